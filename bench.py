@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W                        # BASELINE config #2 per GPU (weak scaling)
     python bench.py --size 768 --batch 8 --chars 12                      # BASELINE config #4
     torchrun ... bench.py --gpus 8 --global-batch 64                     # BASELINE config #3 (one sharded global batch)
+    python bench.py --steps 2 --warmup 1 --dump-outputs out/             # + the last timed step's frames as out/frames.npy
 
 One "step" = one pass of the hot path over one GLOBAL batch of synthetic input.  Default (BASELINE config #2):
 512x512, 50 deterministic Euler (== DDIM eta 0) steps with CFG 5.0, batch 4 per GPU, 9-character labels,
@@ -82,6 +83,9 @@ def parse():
                     "image sharding, the single all-gather per global batch and the JSON line; the numbers mean nothing")
     ap.add_argument("--fuse", type=int, default=1, help="batches concatenated into one UNet call (1 = the on-config "
                     "batch per call; > 1 or 0 = throughput mode, never the headline value)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path returned "
+                    "for its LAST step (the decoded frames of that global batch, [G, 3, H, W]) as DIR/frames.npy in float32 (rank 0), "
+                    "so that two builds can be compared output for output; inputs are seeded, identical for identical arguments")
     return ap.parse_args()
 
 
@@ -118,6 +122,25 @@ def measured_traffic_inflight_plans():
         except Exception:
             continue
     return None, None
+
+
+DUMP_BYTES = 64 * 2 ** 20         # --dump-outputs writes at most this much in all
+DUMP_SAMPLE = 4 * 2 ** 20         # elements kept of a larger output: 16 MB of float32 values + 32 MB of float64 indices
+
+
+def dump_outputs(out_dir: str, outputs: dict) -> None:
+    """write each output as out_dir/<name>.npy in float32.  One that would not fit in DUMP_BYTES is replaced by a fixed, seeded
+    sample of DUMP_SAMPLE of its elements, <name>_sample.npy, with their flat (C-order) indices as <name>_sample_index.npy (float64)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        a = t.detach().float().cpu().contiguous().numpy()
+        if a.nbytes <= DUMP_BYTES // max(len(outputs), 1):
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            continue
+        idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(DUMP_SAMPLE // max(len(outputs), 1), a.size), replace=False))
+        np.save(os.path.join(out_dir, name + "_sample.npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
 
 
 def physical_cores() -> int:
@@ -255,6 +278,8 @@ def stub_main(args, world: int, rank: int) -> None:
     if on:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     assert frames.shape[0] == G
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frames": frames})
     if rank == 0:
         print(json.dumps({"metric": "stub (host logic only)", "value": args.steps * G / float(t.item()), "unit": "images/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": float(t.item()) / args.steps * 1e3,
@@ -345,6 +370,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     assert frames.shape[0] == G and bool(torch.isfinite(frames).all())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frames": frames})
 
     # ---- roofline pass: graph replay issues no per-launch host calls, so the per-kernel HIP events (udt_prof_*,
     # recorded on the launch stream around every launch of the three MFMA classes) are taken on ONE extra pass of one

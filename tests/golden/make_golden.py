@@ -1,10 +1,11 @@
-"""Generate the golden fixtures in tests/golden/ by running the REAL reference (read-only at /root/reference)
+"""Generate the golden fixtures in tests/golden/ by running the REAL reference (a read-only checkout of
+ZYM-PKU/UDiffText, given as UDT_REFERENCE)
 on its CPU path inside the build container.
 
 The reference's Python cannot travel to the GPU box, so only the resulting vectors (inputs are regenerated
 from seeds / the name-keyed synthetic weight recipe, expected outputs are stored) are committed.  Run:
 
-    python tests/golden/make_golden.py            # ~3-4 minutes, needs /root/reference
+    python tests/golden/make_golden.py            # ~3-4 minutes, needs UDT_REFERENCE=<reference checkout>
     python tests/golden/make_golden.py --g11      # only the 50-step trajectory (engine_golden_50.npz), ~3 minutes
     python tests/golden/make_golden.py --g12      # only BASELINE config #2 end to end (engine_golden_512.npz), ~10 minutes
     python tests/golden/make_golden.py --g13      # only the attend-and-excite update (aae_golden.npz), ~2 minutes
@@ -31,7 +32,7 @@ import yaml
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
+REF = os.environ.get("UDT_REFERENCE") or sys.exit("set UDT_REFERENCE to a checkout of the reference (ZYM-PKU/UDiffText)")
 sys.path.insert(0, ROOT)
 
 from udifftext_amd import synth  # noqa: E402

@@ -1,5 +1,6 @@
 """Golden vectors for the OCR scorer, generated in the build container from the REAL reference
-classes of /root/reference/src/parseq (strhub.models.parseq.system.PARSeq, modules.Decoder / DecoderLayer /
+classes of <reference checkout>/src/parseq (UDT_REFERENCE: a checkout of ZYM-PKU/UDiffText;
+strhub.models.parseq.system.PARSeq, modules.Decoder / DecoderLayer /
 TokenEmbedding, strhub.data.utils.Tokenizer):
 
     python tests/golden/make_parseq_golden.py        -> tests/golden/parseq_golden.npz
@@ -24,7 +25,8 @@ import torch.nn.functional as F
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference/src/parseq"
+REF = os.path.join(os.environ.get("UDT_REFERENCE") or sys.exit("set UDT_REFERENCE to a checkout of the reference "
+                                                                "(ZYM-PKU/UDiffText)"), "src", "parseq")
 sys.path.insert(0, ROOT)
 from udifftext_amd import synth  # noqa: E402
 

@@ -54,3 +54,38 @@ def test_bench_cites_the_final_collection_of_the_newest_round(tmp_path, monkeypa
     monkeypatch.setattr(bench, "ROOT", str(tmp_path))
     assert bench.measured_traffic() == (2.0, "r06_traffic.json @ r06_traffic.json")
     assert bench.measured_traffic_inflight_plans()[0] == 5.0
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step_reproducibly(tmp_path):
+    """--dump-outputs DIR writes the frames the timed path returned for its last step as DIR/frames.npy (float32, [G, 3, H, W]);
+    the same arguments give the same arrays, and --steps K makes the K-th timed step the one written"""
+    import numpy as np
+    outs = {}
+    for tag, extra in (("a", []), ("b", []), ("k3", ["--steps", "3"])):
+        d = _run(["--dump-outputs", str(tmp_path / tag)] + extra)
+        assert d["steps"] == (3 if tag == "k3" else 2)
+        assert sorted(os.listdir(tmp_path / tag)) == ["frames.npy"]
+        outs[tag] = np.load(tmp_path / tag / "frames.npy")
+    assert outs["a"].dtype == np.float32 and outs["a"].shape == (4, 3, 4, 4)
+    assert np.array_equal(outs["a"], outs["b"])
+    assert not np.array_equal(outs["a"], outs["k3"])          # step 3's batch and seed, not step 2's
+
+
+def test_bench_dump_outputs_samples_an_output_over_the_budget(tmp_path, monkeypatch):
+    """an output larger than the 64 MB budget is written as a fixed, seeded sample of its elements plus their flat indices"""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 1000)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    t = torch.arange(2 * 3 * 20 * 20, dtype=torch.float32).reshape(2, 3, 20, 20)
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), {"frames": t})
+        assert sorted(os.listdir(tmp_path / tag)) == ["frames_sample.npy", "frames_sample_index.npy"]
+    v, i = np.load(tmp_path / "a" / "frames_sample.npy"), np.load(tmp_path / "a" / "frames_sample_index.npy")
+    assert v.dtype == np.float32 and i.dtype == np.float64 and v.shape == i.shape == (100,)
+    assert np.array_equal(v, t.numpy().reshape(-1)[i.astype(np.int64)])
+    assert np.array_equal(v, np.load(tmp_path / "b" / "frames_sample.npy"))

@@ -2,7 +2,7 @@
 # same-box A/B of one environment switch on the bench: tools/ab_bench_env.sh VAR valueA valueB   (runs A B A B)
 # e.g. tools/ab_bench_env.sh UDT_GN_EPI 1 0   -> gpurun_out/ab_<VAR>.txt
 VAR=$1; A=$2; B=$3
-R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
+R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/gpurun_out
 for v in $A $B $A $B; do
   env $VAR=$v timeout 600 python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-reference-default --no-extra-configs > /tmp/ab_$VAR.json 2> /tmp/ab_$VAR.err

@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of the bench line: bf16 (config #2) vs --fp8 (config #5's arithmetic on one GPU) vs --fp8 with bf16 attention.  usage: tools/ab_fp8.sh <out-dir> [extra bench flags]
-R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/${1:-ab_fp8}; shift
 mkdir -p $O
 cd $R

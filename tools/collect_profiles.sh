@@ -3,7 +3,7 @@
 # per-round yardsticks.   usage: tools/collect_profiles.sh <round-tag> <git HEAD sha>   -> gpurun_out/<tag>/
 # Every file it writes names the commit it was measured at (first line "# HEAD <sha>" for text / csv, a "head" field for json):
 # the box has no .git, so the caller passes `git rev-parse HEAD` (copy what should be judged into profiles/ afterwards).
-R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-r04}
 export UDT_HEAD=${2:-unknown}
 O=$R/gpurun_out/$TAG; mkdir -p $O

@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes over tools/attn_only.py (separate runs per counter group, kernel-trace only): usage tools/pmc_attn.sh <out-dir>
-R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/${1:-pmc_attn}; mkdir -p $O; rm -f $O/counters.txt
 cd /tmp; export TMPDIR=/tmp
 rocprofv3 --list-avail 2>/dev/null | grep -o "SQ_[A-Z_0-9]*\|GRBM_[A-Z_0-9]*\|TCP_[A-Z_0-9]*" | sort -u > $O/avail.txt

@@ -2,7 +2,7 @@
 # L2 hit rate per kernel over a 2-step batch of the bench workload (eager launches, one stream): two PMC passes (TCC_HIT_sum,
 # TCC_MISS_sum; no tracing domains).   usage (GPU box): bash tools/pmc_l2_hit.sh <sha>  > profiles/rNN_l2_hit.txt
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
+R=$(cd "$(dirname "$0")/.." && pwd)
 for c in TCC_HIT_sum TCC_MISS_sum; do
   rm -rf /tmp/l2_$c
   UDT_GRAPHS=0 timeout 300 rocprofv3 --pmc $c --output-format csv -d /tmp/l2_$c -o p -- python $R/tools/predict_once.py 2 > /dev/null 2>&1
