@@ -32,6 +32,8 @@
  *                       guider.prepare_inputs + denoiser scaling + CFG + Euler update
  *                       sgm/modules/diffusionmodules/guiders.py:25-40, denoiser.py:22-28,
  *                       denoiser_scaling.py:16-22, sampling_utils.py:8-9,39-40, sampling.py:85-86,348-351
+ *   udt_cfg_sampler_step  the same CFG denoise + the update of HeunEDMSampler, EulerAncestralSampler,
+ *                       DPMPP2SAncestralSampler, DPMPP2MSampler (sampling.py:140-215,423-567) as one affine form
  *   udt_posterior_sample  DiagonalGaussianDistribution.sample  sgm/modules/distributions/distributions.py:24-41
  *   udt_nchw_to_nhwc / udt_nhwc_to_nchw   layout change at the NCHW fp32 plugin boundary
  *                       (rearrange "b c h w -> b (h w) c", sgm/modules/attention.py:405,412)
@@ -380,6 +382,21 @@ int udt_unet_input(const float* x, void* xin, int32_t B, int32_t hw, int32_t cpa
  *   d = (x - den)/sigma ; x += d*(sigma_next - sigma)          (optionally writes den) */
 int udt_cfg_euler_step(float* x, const float* eps, float* denoised_out, int32_t B, int32_t hw, int32_t ld_eps,
                        float c_out, float sigma, float sigma_next, float cfg_scale, void* stream);
+/* Generic CFG sampler step (one launch per UNet evaluation of any sampler of this package):
+ *   den  = den_u + scale*(den_c - den_u),  den_{u,c} = xin + c_out*eps_{u,c}     (c_out = -quantised sigma)
+ *   xout = kx*xin + kd*den + ka*aux + kp*prev + kn*noise     (a null pointer drops its term)
+ *   den_out = den                                             (optional)
+ * eps fp32 [2B, hw, ld_eps] (uncond half first, 16-byte aligned); xin, aux, prev, noise, xout, den_out fp32 NCHW [B,4,h,w].
+ * xout may alias xin or aux; den_out aliases none of the others.  Coefficients are computed on the host (float64, then
+ * rounded); e.g. Euler ancestral kx = 1 + (s_down - s)/s, kd = -(s_down - s)/s, kn = s_noise*s_up;
+ * DPM++ 2M kx = m1, kd = -m2*m3, kp = m2*m4 (prev = the previous step's den). */
+typedef struct {
+  float kx, kd, ka, kp, kn;
+  float c_out, scale;
+} udt_sampler_coefs;
+int udt_cfg_sampler_step(const float* xin, const float* eps, const float* aux, const float* prev, const float* noise,
+                         float* xout, float* denoised_out, int32_t B, int32_t hw, int32_t ld_eps, udt_sampler_coefs k,
+                         void* stream);
 /* z = scale * (mean + exp(0.5*clamp(logvar,-30,20)) * noise); moments fp32 [B, hw, ldm] NHWC (mean ch 0..3,
  * logvar ch 4..7), noise fp32 NCHW [B,4,h,w], z fp32 NCHW [B,4,h,w]. */
 int udt_posterior_sample(const float* moments, const float* noise, float* z, int32_t B, int32_t hw, int32_t ldm,

@@ -2,6 +2,8 @@
 //
 //   udt_unet_input / udt_cfg_euler_step : guiders.py:25-40, denoiser.py:22-28, denoiser_scaling.py:16-22,
 //                                         sampling_utils.py:8-9,39-40, sampling.py:85-86,348-351
+//   udt_cfg_sampler_step                : the same CFG denoise + the update of any sampler of sampling.py:140-215,423-567
+//                                         as one affine form (host coefficients: udifftext_amd/sgm/.../sampling.py)
 //   udt_posterior_sample                : distributions.py:24-41 (+ LatentEncoder scale, encoders/modules.py:1011-1014)
 //   udt_embed_tokens                    : encoders/modules.py:1069-1085,1160-1163
 //   udt_timestep_embedding              : diffusionmodules/util.py:206-230
@@ -42,6 +44,35 @@ __global__ void cfg_euler_kernel(float* __restrict__ x, const float* __restrict_
     const float d = (xv - den) / sigma;               // to_d, sampling_utils.py:39-40
     xb[c * hw] = xv + d * (sigma_next - sigma);       // euler_step, sampling.py:85-86
     if (den_out) den_out[(long long)b * 4 * hw + c * hw + pix] = den;
+  }
+}
+
+// Generic CFG sampler step: den as in cfg_euler_kernel, then
+//   xout = kx*xin + kd*den + ka*aux + kp*prev + kn*noise   (a null pointer drops its term),  den_out = den.
+// xout may alias xin or aux (each thread reads its pixel's inputs before it writes), so those carry no __restrict__.
+__global__ void cfg_sampler_kernel(const float* xin, const float* __restrict__ eps, const float* aux,
+                                   const float* __restrict__ prev, const float* __restrict__ noise, float* xout,
+                                   float* __restrict__ den_out, int B, int hw, int ld, udt_sampler_coefs k) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * hw) return;
+  const int b = i / hw;
+  const int pix = i - b * hw;
+  const f32x4 eu = *reinterpret_cast<const f32x4*>(eps + ((long long)b * hw + pix) * ld);
+  const f32x4 ec = *reinterpret_cast<const f32x4*>(eps + ((long long)(b + B) * hw + pix) * ld);
+  const long long base = (long long)b * 4 * hw + pix;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const long long o = base + (long long)c * hw;
+    const float xv = xin[o];
+    const float du = eu[c] * k.c_out + xv;
+    const float dc = ec[c] * k.c_out + xv;
+    const float den = du + k.scale * (dc - du);
+    float acc = k.kx * xv + k.kd * den;
+    if (aux) acc += k.ka * aux[o];
+    if (prev) acc += k.kp * prev[o];
+    if (noise) acc += k.kn * noise[o];
+    xout[o] = acc;
+    if (den_out) den_out[o] = den;
   }
 }
 
@@ -252,6 +283,22 @@ extern "C" int udt_cfg_euler_step(float* x, const float* eps, float* denoised_ou
   UDT_STREAM;
   hipLaunchKernelGGL(cfg_euler_kernel, dim3(nblk((long long)B * hw)), dim3(256), 0, s, x, eps, denoised_out, B, hw,
                      ld_eps, c_out, sigma, sigma_next, cfg_scale);
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}
+
+extern "C" int udt_cfg_sampler_step(const float* xin, const float* eps, const float* aux, const float* prev,
+                                    const float* noise, float* xout, float* denoised_out, int32_t B, int32_t hw,
+                                    int32_t ld_eps, udt_sampler_coefs k, void* stream) {
+  if (!xin || !eps || !xout) return UDT_ERR_BAD_ARG;
+  if (B <= 0 || hw <= 0 || ld_eps < 4 || ld_eps % 4 != 0 || (long long)B * hw > 0x7fffffffLL) return UDT_ERR_BAD_SHAPE;
+  if (reinterpret_cast<uintptr_t>(eps) % 16 != 0) return UDT_ERR_BAD_SHAPE;
+  // den_out is written while xin / aux / prev are read by other threads: it may alias none of them (nor xout)
+  if (denoised_out && (denoised_out == xin || denoised_out == aux || denoised_out == prev || denoised_out == xout))
+    return UDT_ERR_BAD_ARG;
+  UDT_STREAM;
+  hipLaunchKernelGGL(cfg_sampler_kernel, dim3(nblk((long long)B * hw)), dim3(256), 0, s, xin, eps, aux, prev, noise, xout,
+                     denoised_out, B, hw, ld_eps, k);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
 }

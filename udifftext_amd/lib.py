@@ -44,6 +44,12 @@ class GemmDesc(C.Structure):
     ]
 
 
+class SamplerCoefs(C.Structure):
+    """udt_sampler_coefs (by value): xout = kx*xin + kd*den + ka*aux + kp*prev + kn*noise"""
+    _fields_ = [("kx", C.c_float), ("kd", C.c_float), ("ka", C.c_float), ("kp", C.c_float), ("kn", C.c_float),
+                ("c_out", C.c_float), ("scale", C.c_float)]
+
+
 # every symbol include/udt_kernels.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _fp = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p
 SYMBOLS = {
@@ -98,6 +104,7 @@ SYMBOLS = {
     "udt_layernorm": (C.c_int, [_vp, _vp, _fp, _fp, _i64, _i32, _f32, _vp]),
     "udt_unet_input": (C.c_int, [_fp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "udt_cfg_euler_step": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
+    "udt_cfg_sampler_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, SamplerCoefs, _vp]),
     "udt_sampler_step": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
     "udt_posterior_sample": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _vp]),
     "udt_nchw_to_nhwc": (C.c_int, [_fp, _vp, _i32, _i32, _i64, _i32, _f32, _vp]),

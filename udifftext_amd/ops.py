@@ -760,6 +760,25 @@ def cfg_euler_step(x: torch.Tensor, eps: torch.Tensor, sigma: float, sigma_next:
             "udt_cfg_euler_step")
 
 
+def cfg_sampler_step(xin: torch.Tensor, eps: torch.Tensor, c_out: float, scale: float, kx: float = 0.0, kd: float = 0.0,
+                     aux: Optional[torch.Tensor] = None, ka: float = 0.0, prev: Optional[torch.Tensor] = None, kp: float = 0.0,
+                     noise: Optional[torch.Tensor] = None, kn: float = 0.0, out: Optional[torch.Tensor] = None,
+                     denoised: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """one launch of udt_cfg_sampler_step: den = CFG(xin + c_out*eps_u, xin + c_out*eps_c);
+    out = kx*xin + kd*den + ka*aux + kp*prev + kn*noise (a term whose tensor is None is absent); denoised <- den.
+    xin / aux / prev / noise / out / denoised: fp32 NCHW [B,4,h,w] contiguous; out defaults to xin (in place)."""
+    B, _, h, w = xin.shape
+    out = xin if out is None else out
+    for t in (xin, aux, prev, noise, out, denoised):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, 4, h, w), "fp32 NCHW [B,4,h,w]"
+    assert eps.dtype == torch.float32 and eps.is_contiguous() and tuple(eps.shape[:-1]) == (2 * B, h, w) and eps.shape[-1] >= 4
+    k = L.SamplerCoefs(kx, kd, ka, kp, kn, c_out, scale)
+    L.check(L.load().udt_cfg_sampler_step(_ptr(xin), _ptr(eps), _ptr(aux), _ptr(prev), _ptr(noise), _ptr(out), _ptr(denoised),
+                                          B, h * w, eps.shape[-1], k, _stream()), "udt_cfg_sampler_step")
+    return out
+
+
 def posterior_sample(moments: torch.Tensor, noise: torch.Tensor, scale: float) -> torch.Tensor:
     """moments fp32 NHWC [B, h, w, ld>=8]; noise fp32 NCHW [B,4,h,w] -> z fp32 NCHW."""
     B, h, w, ld = moments.shape

@@ -38,14 +38,30 @@ def build_engine(device: torch.device, synthetic_weights: bool = True, verbose: 
     return model
 
 
-def init_sampling(steps: int, scale: float, device: torch.device, verbose: bool = False):
-    """reference util.py:24-47: EulerEDMSampler + LegacyDDPMDiscretization + VanillaCFG(scale)"""
-    from sgm.modules.diffusionmodules.sampling import EulerEDMSampler
-    return EulerEDMSampler(
+SAMPLERS = {
+    "euler": "EulerEDMSampler",
+    "dpmpp2m": "DPMPP2MSampler",
+    "heun": "HeunEDMSampler",
+    "euler_a": "EulerAncestralSampler",
+    "dpmpp2s_a": "DPMPP2SAncestralSampler",
+}
+
+
+def init_sampling(steps: int, scale: float, device: torch.device, verbose: bool = False, sampler: str = "euler"):
+    """reference util.py:24-47: EulerEDMSampler + LegacyDDPMDiscretization + VanillaCFG(scale).  ``sampler`` picks another
+    sampler of the reference's sampling.py with the same discretization and guider (SAMPLERS; their default parameters:
+    eta = s_noise = 1 for the ancestral ones, s_churn = 0 for Heun)"""
+    from sgm.modules.diffusionmodules import sampling as S
+    if sampler not in SAMPLERS:
+        raise ValueError(f"unknown sampler {sampler!r}; one of {sorted(SAMPLERS)}")
+    common = dict(
         num_steps=steps,
         discretization_config={"target": "sgm.modules.diffusionmodules.discretizer.LegacyDDPMDiscretization"},
         guider_config={"target": "sgm.modules.diffusionmodules.guiders.VanillaCFG", "params": {"scale": scale}},
-        s_churn=0.0, s_tmin=0.0, s_tmax=999.0, s_noise=1.0, verbose=verbose, device=device)
+        verbose=verbose, device=device)
+    if sampler in ("euler", "heun"):
+        common.update(s_churn=0.0, s_tmin=0.0, s_tmax=999.0, s_noise=1.0)
+    return getattr(S, SAMPLERS[sampler])(**common)
 
 
 def _copy_batch(batch: dict) -> dict:
@@ -88,7 +104,7 @@ def predict(cfgs, model, sampler, batch: dict, device: Optional[torch.device] = 
     c, uc = model.conditioner.get_unconditional_conditioning(
         batch, batch_uc=batch_uc, force_uc_zero_embeddings=cfgs.force_uc_zero_embeddings)
     x = sampler.get_init_noise(cfgs, model, cond=c, batch=batch, uc=uc)
-    z = sampler(model, x, cond=c, batch=batch, uc=uc, init_step=cfgs.init_step, aae_enabled=cfgs.aae_enabled,
+    z = sampler(model, x=x, cond=c, batch=batch, uc=uc, init_step=cfgs.init_step, aae_enabled=cfgs.aae_enabled,
                 detailed=cfgs.detailed)
     img = model.decode_first_stage(z)
     return torch.clamp((img + 1.0) / 2.0, min=0.0, max=1.0), z
@@ -156,6 +172,7 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
     # lanes in lock-stepped groups with a cross-lane join before and after every sampling loop: ~35 ms of each 1.28 s group
     # had no sampling running, and a slow lane held the others.)
     lane_sampler = getattr(sampler, "sample_lane", None)
+    draw_noise = getattr(sampler, "draw_step_noise", None)
     units = [list(range(i, min(i + f, len(batches)))) for i in range(0, len(batches), f)]
     # lanes in use: as few as keep every lane equally loaded — 4 sampling batches on 3 lanes run as 2 + 2 on TWO lanes (each planned
     # for half of the CUs), not as 2 + 1 + 1 with the 4th batch alone on a lane planned for a third of the chip while two lanes idle
@@ -165,7 +182,7 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
         after(lane, main)
     for u, idx in enumerate(units):
         lane = lanes[u % n_used]
-        xs, cs, ucs, sizes = [], [], [], []
+        xs, cs, ucs, sizes, noises = [], [], [], [], []
         with on(lane), ops.launch_context(cu_share=n_used):
             for gi in idx:
                 b, buc = prepare_batch(batches[gi], device)
@@ -174,6 +191,8 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
                     c, uc = model.conditioner.get_unconditional_conditioning(
                         b, batch_uc=buc, force_uc_zero_embeddings=cfgs.force_uc_zero_embeddings)
                     xs.append(sampler.get_init_noise(cfgs, model, cond=c, batch=b, uc=uc))
+                    if draw_noise is not None:      # ancestral samplers: the run's step noise, right after the initial noise
+                        noises.append(draw_noise(xs[-1].shape, xs[-1].device, None, cfgs.init_step))
                 cs.append(c)
                 ucs.append(uc)
                 sizes.append(xs[-1].shape[0])
@@ -182,12 +201,16 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
             fx = torch.cat(xs, 0) if len(xs) > 1 else xs[0]
             fc = _cat_cond(cs) if len(cs) > 1 else cs[0]
             fuc = _cat_cond(ucs) if len(ucs) > 1 else ucs[0]
+            kw = {}
+            if noises and noises[0] is not None:
+                kw["noise"] = torch.cat(noises, 1) if len(noises) > 1 else noises[0]      # [steps, fused batch, 4, h, w]
             if lane_sampler is not None:
-                z = lane_sampler(model, fx, fc, fuc, slot=u % n_used, n_lanes=n_used, init_step=cfgs.init_step, deferred_checks=checks)
+                z = lane_sampler(model, fx, fc, fuc, slot=u % n_used, n_lanes=n_used, init_step=cfgs.init_step, deferred_checks=checks,
+                                 **kw)
             else:       # (stub samplers of the CPU tests: the group interface, one batch at a time)
                 z = sampler.sample_in_flight(model, [fx], [fc], [fuc], init_step=cfgs.init_step, deferred_checks=checks)[0]
             img = torch.clamp((model.decode_first_stage(z) + 1.0) / 2.0, min=0.0, max=1.0)
-        keep.append((xs, cs, ucs, fx, fc, fuc, z))     # tensors of a lane stream: alive until the final synchronisation
+        keep.append((xs, cs, ucs, fx, fc, fuc, z, noises))     # tensors of a lane stream: alive until the final synchronisation
         o = 0
         for nb in sizes:
             out.append((img[o:o + nb], z[o:o + nb]))

@@ -58,6 +58,25 @@ def randn_on(shape: Sequence[int], device) -> torch.Tensor:
     return host.to(device, non_blocking=True)
 
 
+def randn_steps_on(n_steps: int, shape: Sequence[int], device) -> torch.Tensor:
+    """``n_steps`` consecutive ``randn(shape)`` draws (step-major: the values n_steps separate calls would give) as one tensor
+    [n_steps, *shape] on ``device`` — the ancestral samplers' per-step noise of a whole run, drawn up front through one
+    pinned-memory transfer (see ``randn_on``)"""
+    device = torch.device(device)
+    shape = tuple(int(s) for s in shape)
+    gens = _state.gens
+    if gens is not None and len(gens) != shape[0]:
+        raise ValueError(f"per-image noise source holds {len(gens)} generators, draw asks for batch {shape[0]}")
+    host = torch.empty((int(n_steps),) + shape, dtype=torch.float32, pin_memory=device.type == "cuda")
+    for k in range(int(n_steps)):
+        if gens is None:
+            torch.randn(shape, out=host[k])
+        else:
+            for i, g in enumerate(gens):
+                torch.randn((1,) + shape[1:], generator=g, out=host[k, i:i + 1])
+    return host.to(device, non_blocking=True) if device.type == "cuda" else host.to(device)
+
+
 @contextlib.contextmanager
 def per_image(seeds: Sequence[int]):
     """draws inside come from one generator per image (seeded here; each context starts fresh streams)"""

@@ -11,12 +11,16 @@ with the step-invariant pieces hoisted out of the loop (text k|v projections of 
 concat channels of the UNet input).  Attention maps are only emitted where they are consumed (noise search).
 The heavier side paths (attend-and-excite: needs autograd through the UNet; attention-map plots / GIFs) are
 out of scope and raise.
+
+HeunEDMSampler, EulerAncestralSampler, DPMPP2SAncestralSampler and DPMPP2MSampler (reference :140-215, :423-567) run the
+same UNet call followed by ONE udt_cfg_sampler_step launch per evaluation; each supplies a per-step plan of host
+coefficients (``Eval``, bottom of this file).
 """
 from __future__ import annotations
 
 import os
 import sys
-from typing import Dict, Optional, Union
+from typing import Dict, NamedTuple, Optional, Union
 
 import numpy as np
 import torch
@@ -165,9 +169,9 @@ class _Stepper:
             self._emb_cache[idx] = rows
         return rows
 
-    def step(self, x: torch.Tensor, sigma: float, sigma_next: float, emit_maps: bool = False,
-             denoised: Optional[torch.Tensor] = None) -> None:
-        """in-place Euler update of x (fp32 NCHW [B,4,h,w]); denoised (optional): receives the guided denoised latent"""
+    def unet_eps(self, x: torch.Tensor, sigma: float, emit_maps: bool = False):
+        """the CFG pair's UNet call on x (fp32 NCHW [B,4,h,w]) at the quantised sigma -> (eps fp32 NHWC [2B,h,w,ld],
+        quantised sigma)"""
         idx, sq = self.quantise(sigma)
         c_in = 1.0 / (sq * sq + 1.0) ** 0.5
         ops.unet_input(x, self.xin, c_in)
@@ -180,7 +184,26 @@ class _Stepper:
             with ops.launch_context(cu_share=self.cu_share, workspace=self.ws):
                 eps = self.unet.forward_nhwc(self.xin, emb, self.t_kv, emit_maps=emit_maps,
                                              zero_ctx_rows=self.zero_ctx_rows, t_fused=self.t_fused)
+        return eps, sq
+
+    def step(self, x: torch.Tensor, sigma: float, sigma_next: float, emit_maps: bool = False,
+             denoised: Optional[torch.Tensor] = None) -> None:
+        """in-place Euler update of x (fp32 NCHW [B,4,h,w]); denoised (optional): receives the guided denoised latent"""
+        eps, sq = self.unet_eps(x, sigma, emit_maps)
         ops.cfg_euler_step(x, eps, sigma, sigma_next, self.scale, denoised=denoised, c_out=-sq)
+
+    def run_plan(self, bufs: Dict[str, torch.Tensor], plan, noise: Optional[torch.Tensor] = None) -> None:
+        """one step of a non-Euler sampler: per evaluation of ``plan`` (a tuple of ``Eval``), the UNet call on its source buffer
+        and one udt_cfg_sampler_step launch; ``bufs`` maps the plan's buffer names to fp32 NCHW tensors, ``noise`` is this
+        step's ancestral draw"""
+        for e in plan:
+            src = bufs[e.src]
+            eps, sq = self.unet_eps(src, e.sigma)
+            ops.cfg_sampler_step(src, eps, -sq, self.scale, e.kx, e.kd,
+                                 aux=bufs[e.aux] if e.aux else None, ka=e.ka,
+                                 prev=bufs[e.prev] if e.prev else None, kp=e.kp,
+                                 noise=noise if e.kn != 0.0 else None, kn=e.kn,
+                                 out=bufs[e.out], denoised=bufs[e.den_out] if e.den_out else None)
 
     def check(self) -> None:
         """synchronise and raise if a stream-K launch of this stepper timed out (library err word)"""
@@ -657,3 +680,352 @@ class EulerEDMSampler(EDMSampler):
         """drop every captured hipGraph (explicit hook; the caches also notice changed weights by fingerprint)"""
         self.__dict__.pop("_graphed", None)
         self.__dict__.pop("_in_flight", None)
+
+
+# ================================================================================================ the other samplers
+# HeunEDMSampler, EulerAncestralSampler, DPMPP2SAncestralSampler and DPMPP2MSampler (reference sampling.py:140-215,
+# 423-567).  Every UNet evaluation of any of them is ONE udt_cfg_sampler_step launch after the UNet call:
+#     den  = CFG(xin + c_out*eps_u, xin + c_out*eps_c)                  (c_out = -quantised sigma)
+#     xout = kx*xin + kd*den + ka*aux + kp*prev + kn*noise
+# A sampler only supplies its per-step ``plan``: the evaluations of step i with their sigma and float64 host coefficients, over
+# four named fp32 NCHW buffers — "x" (the latent), "t" (Euler predictor / midpoint) and "h0" / "h1" (denoised history).  The same
+# plan runs as eager launches, inside one hipGraph per (step index, plan), or (tests) as plain torch arithmetic.
+
+
+class Eval(NamedTuple):
+    """one UNet evaluation + its fused update: out = kx*src + kd*den(src, sigma) + ka*aux + kp*prev + kn*noise[step]"""
+    sigma: float                       # UNQUANTISED sigma of the call (c_in, c_out and the timestep use its quantised value)
+    src: str
+    out: str
+    kx: float = 0.0
+    kd: float = 0.0
+    aux: Optional[str] = None
+    ka: float = 0.0
+    prev: Optional[str] = None
+    kp: float = 0.0
+    kn: float = 0.0
+    den_out: Optional[str] = None
+
+
+def ancestral_step(sigma: float, sigma_next: float, eta: float):
+    """reference sampling_utils.get_ancestral_step in float64 -> (sigma_down, sigma_up)"""
+    if not eta:
+        return sigma_next, 0.0
+    up = min(sigma_next, eta * (sigma_next ** 2 * (sigma ** 2 - sigma_next ** 2) / sigma ** 2) ** 0.5)
+    return max(sigma_next ** 2 - up ** 2, 0.0) ** 0.5, up
+
+
+def _euler_to(sigma: float, target: float):
+    """x + (x - den)/sigma * (target - sigma) as (kx, kd)"""
+    r = (target - sigma) / sigma
+    return 1.0 + r, -r
+
+
+class _GraphedPlan(_GraphedSteps):
+    """hipGraph replay of a plan-driven sampler: one graph per (step index, plan); besides the latent, the scratch / history
+    buffers and the run's ancestral noise ([steps, B, 4, h, w], refreshed per run) are static"""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.bufs = {"x": self.x}
+        for k in ("t", "h0", "h1"):
+            self.bufs[k] = torch.zeros_like(self.x)
+        self.noise = torch.zeros((len(self.sig) - 1,) + tuple(self.x.shape), dtype=torch.float32, device=self.st.dev)
+
+    def load(self, x: torch.Tensor, noise: Optional[torch.Tensor], init_step: int) -> None:
+        self.x.copy_(x)
+        if noise is not None:
+            self.noise[init_step:].copy_(noise)
+
+    def capture_plan(self, i: int, plan) -> None:
+        st = self.st
+        for e in plan:
+            st.emb_rows(st.quantise(e.sigma)[0])             # time-embedding rows are cached outside the graph
+        if not self.warm:
+            torch.cuda.synchronize()
+            with torch.cuda.stream(self.capture_stream):
+                keep = {k: v.clone() for k, v in self.bufs.items()}
+                st.run_plan(self.bufs, plan, self.noise[i])
+                for k, v in keep.items():
+                    self.bufs[k].copy_(v)
+            torch.cuda.synchronize()
+            self.warm = True
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self.pool, stream=self.capture_stream, capture_error_mode="thread_local"):
+            st.run_plan(self.bufs, plan, self.noise[i])
+        self.graphs[(i, plan)] = g
+
+
+class _PlanSampler:
+    """the sampling loop of the plan-driven samplers: __call__, the noise-search initial noise (shared with EulerEDMSampler:
+    it does not depend on the sampler), hipGraph replay, and the lanes of pipeline.predict_many / sample_in_flight"""
+    use_graphs = os.environ.get("UDT_GRAPHS", "1") != "0"
+    uses_noise = False                 # ancestral samplers: one rng draw [B,4,h,w] per step, the last step included
+
+    get_init_noise = EulerEDMSampler.get_init_noise
+    _host_sigmas = EulerEDMSampler._host_sigmas
+    release_retired = EulerEDMSampler.release_retired
+    invalidate_graphs = EulerEDMSampler.invalidate_graphs
+
+    def step_plan(self, sig, i: int, init_step: int = 0) -> tuple:
+        """the evaluations of step i (sig: host sigmas, len num_steps + 1) -> tuple of Eval"""
+        raise NotImplementedError
+
+    def _check_fast_path(self):
+        if not isinstance(self.guider, VanillaCFG):
+            raise NotImplementedError("the fused MI355X step implements VanillaCFG guidance")
+        if getattr(self, "s_churn", 0.0) != 0.0:
+            raise NotImplementedError("s_churn > 0 (stochastic sampling) is not implemented for the fused samplers")
+
+    def _check_options(self, aae_enabled, detailed):
+        if aae_enabled:
+            raise NotImplementedError(f"attend-and-excite is implemented for EulerEDMSampler only, not {type(self).__name__}")
+        if detailed:
+            raise NotImplementedError(f"detailed attention-map dumps are implemented for EulerEDMSampler only, not {type(self).__name__}")
+
+    def draw_step_noise(self, shape, device, num_steps=None, init_step: int = 0) -> Optional[torch.Tensor]:
+        """the ancestral draws of one run: one rng.randn of ``shape`` per step from init_step on, in step order, as ONE device
+        buffer [steps, *shape] (None for the deterministic samplers).  Drawn up front so that graph replays can read a slice
+        per step; the values equal per-step draws because the CPU streams are sequential."""
+        if not self.uses_noise:
+            return None
+        n = len(self._host_sigmas(num_steps)) - 1 - init_step
+        return rng.randn_steps_on(n, shape, device)
+
+    def plans(self, sig, init_step: int = 0):
+        return [(i, self.step_plan(sig, i, init_step)) for i in self.get_sigma_gen(len(sig), init_step=init_step)]
+
+    # --------------------------------------------------------------------------------------------- loop
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, init_step=0, batch=None, aae_enabled=False, detailed=False,
+                 name=None, noise: Optional[torch.Tensor] = None, **kwargs):
+        """reference __call__(denoiser, x, cond, uc, num_steps) [+ init_step]; ``noise``: the run's ancestral draws
+        (draw_step_noise), drawn here when not given"""
+        self._check_options(aae_enabled, detailed)
+        self._check_fast_path()
+        require_gpu(x, type(self).__name__)
+        model = denoiser
+        uc = default(uc, cond)
+        sig = self._host_sigmas(num_steps)
+        x = x.float().contiguous()
+        if noise is None:
+            noise = self.draw_step_noise(x.shape, x.device, num_steps, init_step)
+        x *= (1.0 + sig[0] ** 2.0) ** 0.5
+        plans = self.plans(sig, init_step)
+        if self.use_graphs:
+            out = self._run_graphed(model, x, cond, uc, sig, init_step, plans, noise)
+            if out is not None:
+                return out
+        stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale)
+        bufs = {"x": x, "t": torch.empty_like(x), "h0": torch.empty_like(x), "h1": torch.empty_like(x)}
+        for i, plan in plans:
+            stepper.run_plan(bufs, plan, noise[i - init_step] if noise is not None else None)
+        stepper.check()
+        return x
+
+    def _run_graphed(self, model, x, cond, uc, sig, init_step, plans, noise):
+        key = (id(model), tuple(x.shape), len(sig), float(self.guider.scale), tuple(sig[:2]), x.device.index)
+        cache = self.__dict__.setdefault("_graphed", {})
+        try:
+            gs = cache.get(key)
+            if gs is not None and gs.fingerprint != weights_fingerprint(model):
+                gs = None
+            if gs is None or not gs.rebind(cond, uc):
+                cache.clear()
+                gs = _GraphedPlan(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale, sig)
+                cache[key] = gs
+            gs.load(x, noise, init_step)
+            for i, plan in plans:
+                g = gs.graphs.get((i, plan))
+                if g is None:
+                    gs.capture_plan(i, plan)
+                    g = gs.graphs[(i, plan)]
+                g.replay()
+            out = gs.x.clone()
+            gs.st.check()
+            return out
+        except RuntimeError as e:
+            if not _is_capture_failure(e):
+                raise
+            if not self.__dict__.get("_graph_warned"):
+                print(f"[udifftext_amd] hipGraph capture unavailable ({e}); using eager launches", file=sys.stderr)
+                self._graph_warned = True
+            self.use_graphs = False
+            cache.clear()
+            return None
+
+    # ------------------------------------------------------------------------------- batches in flight
+    def _lane_runner(self, model, x, cond, uc, slot, n_lanes, sig, plans, retired):
+        """this lane's graph runner, rebound to the batch, with every graph of ``plans`` captured"""
+        cache = self.__dict__.setdefault("_in_flight", {})
+        fp = weights_fingerprint(model)
+        key = (slot, n_lanes, id(model), tuple(x.shape), len(sig), float(self.guider.scale), tuple(sig[:2]), x.device.index)
+        gs = cache.get(key)
+        if gs is not None and gs.fingerprint != fp:            # weights changed: the captured pointers are stale
+            retired.append(cache.pop(key))
+            gs = None
+        if gs is None or not gs.rebind(cond, uc):
+            gs = _GraphedPlan(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale, sig, cu_share=n_lanes)
+            if key in cache:
+                retired.append(cache.pop(key))
+            victims = [k for k in cache if not (k[1] == n_lanes and k[2] == id(model) and k[3] == tuple(x.shape))]
+            while len(cache) >= 8 and victims:                  # every runner owns a memory pool: keep the newest few
+                retired.append(cache.pop(victims.pop(0)))
+            cache[key] = gs
+        missing = [(i, p) for i, p in plans if (i, p) not in gs.graphs]
+        if missing:
+            lane = torch.cuda.current_stream()
+            gs.capture_stream.wait_stream(lane)
+            for i, p in missing:
+                gs.capture_plan(i, p)
+            lane.wait_stream(gs.capture_stream)
+        return gs
+
+    def sample_lane(self, model, x, cond, uc, slot: int, n_lanes: int, init_step=0, deferred_checks: Optional[list] = None,
+                    noise: Optional[torch.Tensor] = None):
+        """EulerEDMSampler.sample_lane for this sampler: the loop of ONE batch on the CURRENT stream as lane ``slot`` of
+        ``n_lanes``, no host synchronisation; ``noise``: the batch's ancestral draws (drawn here when not given)"""
+        if n_lanes <= 1 or not self.use_graphs:
+            return self(model, x, cond=cond, uc=uc, init_step=init_step, noise=noise)
+        self._check_fast_path()
+        require_gpu(x, type(self).__name__)
+        uc = default(uc, cond)
+        sig = self._host_sigmas(None)
+        if noise is None:
+            noise = self.draw_step_noise(x.shape, x.device, None, init_step)
+        plans = self.plans(sig, init_step)
+        retired = self.__dict__.setdefault("_retired", [])
+        retired[:] = [r for r in retired if getattr(r, "last_replay", None) is not None and not r.last_replay.query()]
+        gs = self._lane_runner(model, x, cond, uc, slot, n_lanes, sig, plans, retired)
+        lane = torch.cuda.current_stream()
+        gs.load(x.float(), noise, init_step)
+        gs.x.mul_((1.0 + sig[0] ** 2.0) ** 0.5)
+        for i, p in plans:
+            gs.graphs[(i, p)].replay()
+        out = gs.x.clone()
+        gs.last_replay = torch.cuda.Event()
+        gs.last_replay.record(lane)
+        if deferred_checks is not None:
+            if gs.st.check not in deferred_checks:
+                deferred_checks.append(gs.st.check)
+        else:
+            gs.st.check()
+        return out
+
+    def sample_in_flight(self, model, xs, conds, ucs, init_step=0, deferred_checks: Optional[list] = None,
+                         streams: Optional[list] = None, noises: Optional[list] = None):
+        """EulerEDMSampler.sample_in_flight for this sampler: several independent batches, one launch stream each, graph
+        replays interleaved step by step; ``noises[k]``: batch k's ancestral draws (drawn here, in batch order, when not given)"""
+        n = len(xs)
+        if noises is None:
+            noises = [self.draw_step_noise(x.shape, x.device, None, init_step) for x in xs]
+        if n == 1 or not self.use_graphs:
+            return [self(model, x, cond=c, uc=u, init_step=init_step, noise=nz) for x, c, u, nz in zip(xs, conds, ucs, noises)]
+        self._check_fast_path()
+        sig = self._host_sigmas(None)
+        plans = self.plans(sig, init_step)
+        retired = self.__dict__.setdefault("_retired", [])
+        main = torch.cuda.current_stream()
+        runners = []
+        for slot, (x, c, u, nz) in enumerate(zip(xs, conds, ucs, noises)):
+            require_gpu(x, type(self).__name__)
+            gs = self._lane_runner(model, x, c, default(u, c), slot, n, sig, plans, retired)
+            gs.load(x.float(), nz, init_step)
+            gs.x.mul_((1.0 + sig[0] ** 2.0) ** 0.5)
+            runners.append(gs)
+        lanes = list(streams[:n]) if streams is not None and len(streams) >= n else [gs.capture_stream for gs in runners]
+        for lane in lanes:
+            lane.wait_stream(main)
+        for i, p in plans:                               # interleaved launches: every queue stays fed
+            for gs, lane in zip(runners, lanes):
+                with torch.cuda.stream(lane):
+                    gs.graphs[(i, p)].replay()
+        for lane in lanes:
+            main.wait_stream(lane)
+        outs = [gs.x.clone() for gs in runners]
+        for gs in runners:
+            if deferred_checks is not None:
+                deferred_checks.append(gs.st.check)
+            else:
+                gs.st.check()
+        return outs
+
+
+class HeunEDMSampler(_PlanSampler, EDMSampler):
+    """reference sampling.py:423-441 (s_churn = 0): Euler predictor, then the trapezoidal corrector with a second evaluation at
+    sigma_next — 2 evaluations per step, 1 on the last (sigma_next = 0)"""
+
+    def step_plan(self, sig, i, init_step=0):
+        s, sn = float(sig[i]), float(sig[i + 1])
+        kx, kd = _euler_to(s, sn)
+        if sn < 1e-14:
+            return (Eval(s, "x", "x", kx=kx, kd=kd),)
+        dt = sn - s
+        return (Eval(s, "x", "t", kx=kx, kd=kd, den_out="h0"),                       # t = Euler predictor, h0 = den
+                # x + dt/2 * ((x - den)/s + (t - den2)/sn)
+                Eval(sn, "t", "x", kx=dt / (2 * sn), kd=-dt / (2 * sn), aux="x", ka=1.0 + dt / (2 * s), prev="h0",
+                     kp=-dt / (2 * s)))
+
+
+class AncestralSampler(_PlanSampler, SingleStepDiffusionSampler):
+    """reference sampling.py:140-175: eta, s_noise; noise_sampler is rng.randn (drawn up front, draw_step_noise)"""
+    uses_noise = True
+
+    def __init__(self, eta=1.0, s_noise=1.0, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.eta = eta
+        self.s_noise = s_noise
+
+    def _noise_coef(self, sigma_next, sigma_up):
+        return self.s_noise * sigma_up if sigma_next > 0.0 else 0.0         # torch.where(next_sigma > 0, ...)
+
+
+class EulerAncestralSampler(AncestralSampler):
+    """reference sampling.py:444-452: Euler to sigma_down, then + s_noise * sigma_up * noise — 1 evaluation per step"""
+
+    def step_plan(self, sig, i, init_step=0):
+        s, sn = float(sig[i]), float(sig[i + 1])
+        down, up = ancestral_step(s, sn, self.eta)
+        kx, kd = _euler_to(s, down)
+        return (Eval(s, "x", "x", kx=kx, kd=kd, kn=self._noise_coef(sn, up)),)
+
+
+class DPMPP2SAncestralSampler(AncestralSampler):
+    """reference sampling.py:455-494: second-order singlestep DPM-Solver++ with the midpoint evaluation at
+    to_sigma(t + h/2) — 2 evaluations per step, 1 where sigma_down = 0"""
+
+    def step_plan(self, sig, i, init_step=0):
+        s, sn = float(sig[i]), float(sig[i + 1])
+        down, up = ancestral_step(s, sn, self.eta)
+        kn = self._noise_coef(sn, up)
+        if down < 1e-14:
+            kx, kd = _euler_to(s, down)
+            return (Eval(s, "x", "x", kx=kx, kd=kd, kn=kn),)
+        t, t_next = -np.log(s), -np.log(down)
+        h = t_next - t
+        s_mid = t + 0.5 * h
+        m1 = float(np.exp(-s_mid) / np.exp(-t))
+        m2 = float(np.expm1(-0.5 * h))
+        m3 = float(np.exp(-t_next) / np.exp(-t))
+        m4 = float(np.expm1(-h))
+        return (Eval(s, "x", "t", kx=m1, kd=-m2),                                   # x2 = m1*x - m2*den
+                Eval(float(np.exp(-s_mid)), "t", "x", kd=-m4, aux="x", ka=m3, kn=kn))   # m3*x - m4*den2 (+ noise)
+
+
+class DPMPP2MSampler(_PlanSampler, BaseDiffusionSampler):
+    """reference sampling.py:497-567: second-order multistep DPM-Solver++ — 1 evaluation per step; the previous step's
+    denoised latent is the history (two static buffers, ping-pong by step parity)"""
+
+    def step_plan(self, sig, i, init_step=0):
+        s, sn = float(sig[i]), float(sig[i + 1])
+        hist, old = f"h{i % 2}", f"h{(i - 1) % 2}"
+        if sn < 1e-14:                                   # log 0: m1 = 0, m2 = -1 -> x = den
+            return (Eval(s, "x", "x", kx=0.0, kd=1.0, den_out=hist),)
+        t, t_next = -np.log(s), -np.log(sn)
+        h = t_next - t
+        m1 = float(np.exp(-t_next) / np.exp(-t))
+        m2 = float(np.expm1(-h))
+        if i == init_step:                               # no history yet: x_standard
+            return (Eval(s, "x", "x", kx=m1, kd=-m2, den_out=hist),)
+        r = (t - (-np.log(float(sig[i - 1])))) / h
+        m3, m4 = 1.0 + 1.0 / (2.0 * r), 1.0 / (2.0 * r)
+        return (Eval(s, "x", "x", kx=m1, kd=-m2 * m3, prev=old, kp=m2 * m4, den_out=hist),)
