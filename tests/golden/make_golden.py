@@ -10,6 +10,8 @@ from seeds / the name-keyed synthetic weight recipe, expected outputs are stored
     python tests/golden/make_golden.py --g12      # only BASELINE config #2 end to end (engine_golden_512.npz), ~10 minutes
     python tests/golden/make_golden.py --g13      # only the attend-and-excite update (aae_golden.npz), ~2 minutes
     python tests/golden/make_golden.py --g14      # only the training step's loss and parameter gradients (train_golden.npz), ~2 minutes
+    python tests/golden/make_golden.py --g15      # only the iterated forms: attend-and-excite loop exits, the sampler's
+                                                  # attend-and-excite schedule, three AdamW steps (iterated_golden.npz), ~2 minutes
 
 Import recipe: import transformers first; stub the absent third-party modules
 (pytorch_lightning, omegaconf, kornia, open_clip, imageio, seaborn, torchvision, timm); replace xformers'
@@ -295,7 +297,212 @@ def g14(model, t0):
           + f"; {len(names)} trained tensors, |grad| rms full {np.sqrt(out['g14_full_stats'][:, 2].sum() / sum(p_.numel() for p_ in params)):.3e}")
 
 
-def main(only_g11: bool = False, only_g12: bool = False, only_g13: bool = False, only_g14: bool = False):
+# G15c: the optimiser of the three training steps (a legal reference configuration, diffusion.py:197-219).  eps >= 10x the largest
+# |gradient| of step 1 makes Adam's update linear in the gradient (with eps = 1e-8 the first step is lr * sign(g): a near-zero element
+# whose sign differs at bf16 accuracy would move by a full lr); lr makes the loss move by >= 10x the test's loss tolerance per step
+G15C_LR, G15C_EPS, G15C_WD = 1.6e-2, 1.0, 1e-2
+G15C_GRAD_SUB, G15C_DP_SUB = 256, 128  # sub-sample sizes of the stored gradients / p_k - p_0 per trained tensor (keeps the file ~0.4 MB)
+# the free-running tolerances of tests/test_iterated_gpu.py at steps 2 and 3 (TOL_LOSS_FREE, relative; TOL_GRAD_FREE, rel rms): the
+# previous update must move the loss and the gradients by >= 3x / 5x them.  (10x is out of reach at any lr: the free-running
+# tolerances grow with the update itself, G TOL_STEP — tests/error_budget_iterated.py)
+G15C_LOSS_TOL, G15C_GRAD_TOL = 6.7e-3, 7.4e-2
+
+
+def g15(model, S, t0):
+    """G15 — the ITERATED forms of SURVEY 8f-4 (every real use of the reverse pass is a loop):
+    G15a: the real EulerEDMSampler.attend_and_excite loop (reference sampling.py:233-252) at the G13 point (``aae_batch()``, 16x16
+    latents, B = 1, step 2 of 10, the G13 conditioning), under a torch.autograd.grad recorder, for (i) iter_enabled, thres = +1e3:
+    ends on ``loss <= thres`` after one update; (ii) iter_enabled, thres = -1e3, max_iter = 2: ends on ``iters > max_iter`` after
+    three updates ((iii) iter_enabled = False is G13).  Stored per iteration k: the x_k the gradient was taken at, the loss, the
+    gradient; and the final x.
+    G15b: the real EulerEDMSampler.__call__ with aae_enabled = True, 50 steps, on ``aae_batch()``, its attend_and_excite replaced by a
+    recorder of (i, sigma, alpha, iter_enabled, thres) that returns x unchanged (forward passes only).  Stored: the call list, the
+    initial noise, the per-step local losses the reference computes (sampler_step's third result) and the final latent.
+    G15c: three training steps from G14's inputs (``train_batch()``, B = 2): FullLoss.__call__ with lambda_local_loss = 0 (the smooth
+    loss), ``backward()``, and the optimiser the reference's own configure_optimizers() builds (AdamW, lr / eps above), stepped by
+    opt.step(); scheduler.step() once between steps 2 and 3 (LambdaLR 0.95^epoch).  Step 1 uses G14's draws, steps 2 / 3 their own.
+    Stored per step: the loss dict; per trained tensor [sum, sum |.|, sum squares] + the ``sub()`` sample of the gradient (256 values;
+    step 1's is G14's 512-value ``g14_diff_sub``) and of p_k - p_0 (128 values).  Inputs already in aae_golden.npz / train_golden.npz (the
+    conditioning of G13 and G14) are not stored again."""
+    import contextlib
+    import io
+    batch = aae_batch()
+    torch.manual_seed(1234)
+    buc = {k: (v.clone() if isinstance(v, torch.Tensor) else list(v)) for k, v in batch.items()}
+    buc["label"] = ["" for _ in batch["label"]]
+    buc["txt"] = ["" for _ in batch["txt"]]
+    c, uc = model.conditioner.get_unconditional_conditioning(batch, batch_uc=buc, force_uc_zero_embeddings=["label"])
+    g13 = np.load(os.path.join(HERE, "aae_golden.npz"))
+    assert np.array_equal(c["concat"].numpy(), g13["g13_c_concat"]) and np.array_equal(c["t_crossattn"].numpy(), g13["g13_c_txt"])
+    mk = lambda: S.EulerEDMSampler(
+        num_steps=10,
+        discretization_config={"target": "sgm.modules.diffusionmodules.discretizer.LegacyDDPMDiscretization"},
+        guider_config={"target": "sgm.modules.diffusionmodules.guiders.VanillaCFG", "params": {"scale": 5.0}},
+        s_churn=0.0, s_tmin=0.0, s_tmax=999.0, s_noise=1.0, verbose=False, device="cpu")
+    out = {}
+    # ---------------------------------------------------------------- G15a
+    sampler = mk()
+    x = torch.from_numpy(g13["g13_x"])
+    sigma = torch.from_numpy(g13["g13_sigma"])
+    alpha = float(g13["g13_alpha"][0])
+    real_grad = torch.autograd.grad
+    for tag, thres, max_iter, n_expect in (("i", 1e3, 20, 1), ("ii", -1e3, 2, 3)):
+        rec = []
+
+        def recording_grad(*a, **k):
+            r = real_grad(*a, **k)
+            rec.append((a[1][0].detach().clone(), a[0].detach().clone().reshape(-1), r[0].detach().clone()))
+            return r
+        with torch.enable_grad():
+            torch.autograd.grad = recording_grad
+            try:
+                xf = sampler.attend_and_excite(x, model, sigma, c, {"mask": batch["mask"], "seg_mask": batch["seg_mask"]}, alpha, True,
+                                               thres, max_iter=max_iter)
+            finally:
+                torch.autograd.grad = real_grad
+        assert len(rec) == n_expect, (tag, len(rec))
+        assert torch.equal(rec[0][0], x) and torch.equal(rec[0][2], torch.from_numpy(g13["g13_grad"]))
+        out[f"g15a_{tag}_x"] = torch.stack([r[0] for r in rec]).numpy()
+        out[f"g15a_{tag}_loss"] = torch.cat([r[1] for r in rec]).numpy()
+        out[f"g15a_{tag}_grad"] = torch.stack([r[2] for r in rec]).numpy()
+        out[f"g15a_{tag}_x_final"] = xf.detach().numpy()
+        print(f"[golden] G15a ({tag}) {len(rec)} updates, losses {out[f'g15a_{tag}_loss']} ({time.time() - t0:.1f}s)", flush=True)
+    out.update({"g15a_sigma": sigma.numpy(), "g15a_alpha": np.array([alpha])})           # (conditioning: G13's, asserted above)
+    out["g15a_thres"] = np.array([1e3, -1e3])
+    out["g15a_max_iter"] = np.array([20, 2])
+    # ---------------------------------------------------------------- G15b
+    s50 = S.EulerEDMSampler(
+        num_steps=50,
+        discretization_config={"target": "sgm.modules.diffusionmodules.discretizer.LegacyDDPMDiscretization"},
+        guider_config={"target": "sgm.modules.diffusionmodules.guiders.VanillaCFG", "params": {"scale": 5.0}},
+        s_churn=0.0, s_tmin=0.0, s_tmax=999.0, s_noise=1.0, verbose=False, device="cpu")
+    cur, calls, losses = {}, [], []
+    real_gen, real_step = s50.get_sigma_gen, s50.sampler_step
+
+    def sigma_gen(*a, **k):
+        for i in real_gen(*a, **k):
+            cur["i"] = i
+            yield i
+
+    def recording_aae(x_, model_, sigma_, cond_, batch_, alpha_, iter_enabled_, thres_, max_iter=20):
+        calls.append((cur["i"], float(sigma_.reshape(-1)[0]), float(alpha_), float(bool(iter_enabled_)), float(thres_)))
+        return x_
+
+    def recording_step(*a, **k):
+        r = real_step(*a, **k)
+        losses.append(float(r[2].reshape(-1)[0]))
+        return r
+    s50.get_sigma_gen, s50.attend_and_excite, s50.sampler_step = sigma_gen, recording_aae, recording_step
+    sys.modules["imageio"].mimsave = lambda *a, **k: None          # (the reference writes the decoded intermediates as a GIF)
+    x0 = torch.randn((1, 4, 16, 16), generator=torch.Generator().manual_seed(15))
+    with contextlib.redirect_stdout(io.StringIO()):
+        zb = s50(model, x0.clone(), cond=c, batch=batch, uc=uc, init_step=0, aae_enabled=True, detailed=False)
+    assert len(calls) == 50 and len(losses) == 50 and [cl[0] for cl in calls] == list(range(50))
+    assert sum(cl[3] for cl in calls) == 6
+    out["g15b_x0"] = x0.numpy()
+    assert not bool(uc["t_crossattn"].any())                          # (conditioning: G13's c; uc's text context is zero)
+    out["g15b_uc_concat"] = uc["concat"].numpy()
+    out["g15b_calls"] = np.array(calls, dtype=np.float64)
+    out["g15b_local_losses"] = np.array(losses, dtype=np.float64)
+    out["g15b_latent"] = zb.numpy()
+    print(f"[golden] G15b 50-step attend-and-excite schedule done ({time.time() - t0:.1f}s): iterated at "
+          f"{[int(cl[0]) for cl in calls if cl[3]]}, losses {losses[0]:.6f} .. {losses[-1]:.6f}", flush=True)
+    # ---------------------------------------------------------------- G15c
+    tb = train_batch()
+    g14 = np.load(os.path.join(HERE, "train_golden.npz"))
+    torch.manual_seed(4321)
+    z = torch.randn((2, 4, 16, 16)) * 0.8
+    noise1 = torch.randn((2, 4, 16, 16))                   # (G14's draw order: the conditioner's ucg draw comes next)
+    assert np.array_equal(z.numpy(), g14["g14_z"]) and np.array_equal(noise1.numpy(), g14["g14_noise"])
+    gen = torch.Generator().manual_seed(1515)
+    draws = [(torch.tensor([700, 250]), noise1)]
+    for _ in range(2):
+        draws.append((torch.randint(0, 1000, (2,), generator=gen), torch.randn((2, 4, 16, 16), generator=gen)))
+    loss_fn = model.loss_fn
+    loss_fn.lambda_local_loss = 0.0
+    sigmas_tab = model.denoiser.sigmas
+    model.learning_rate = G15C_LR
+    model.optimizer_config = {"target": "torch.optim.AdamW", "params": {"eps": G15C_EPS}}
+    model.opt_keys = ["t_attn", "t_norm"]                   # (configs/train/textdesign_sd_2.yaml:4-6; the test config lists t_attn)
+    with contextlib.redirect_stdout(io.StringIO()):
+        (opt,), scheduler = model.configure_optimizers()
+    named = [("model." + n, p_) for n, p_ in model.model.named_parameters() if any(k in n for k in ("t_attn", "t_norm"))]
+    names, params = [n for n, _ in named], [p_ for _, p_ in named]
+    assert names == [str(n) for n in g14["g14_names"]]
+    assert [id(p_) for p_ in opt.param_groups[0]["params"]] == [id(p_) for p_ in params]      # (no trainable embedder)
+    assert opt.defaults["weight_decay"] == G15C_WD and opt.defaults["eps"] == G15C_EPS
+    p0 = [p_.detach().clone() for p_ in params]
+    recorded = {}
+    real_cond = model.conditioner.forward
+
+    def cond_once(b, *a, **k):
+        if "cond" not in recorded:
+            recorded["cond"] = real_cond(b, *a, **k)
+        return recorded["cond"]
+    real_randn_like = torch.randn_like
+    cur_draw = {}
+    loss_fn.sigma_sampler = lambda n, rand=None: sigmas_tab[cur_draw["idx"]]
+    full, stale, stale_gd = [], [], []
+    try:
+        model.conditioner.forward = cond_once
+        torch.randn_like = lambda t, **k: cur_draw["noise"].clone()
+        for p_ in params:
+            p_.requires_grad_(True)
+        with torch.enable_grad():
+            for k, (idx, noise) in enumerate(draws):
+                cur_draw["idx"], cur_draw["noise"] = idx, noise
+                if k == 2:
+                    scheduler.step()                                   # epoch 1: lr * 0.95
+                opt.zero_grad(set_to_none=True)
+                loss, ld = loss_fn(model.model, model.denoiser, model.conditioner, z, tb, model.first_stage_model, model.scale_factor)
+                loss.backward()
+                gs = [p_.grad.detach().clone() for p_ in params]
+                if k == 0:
+                    gmax = max(float(g_.abs().max()) for g_ in gs)
+                    assert 10 * gmax <= G15C_EPS, (gmax, G15C_EPS)
+                    ref14 = torch.from_numpy(g14["g14_diff_sub"])
+                    assert all(torch.allclose(gsub(g_), ref14[i, :gsub(g_).numel()], rtol=1e-5, atol=1e-9) for i, g_ in enumerate(gs))
+                if k > 0:
+                    num = sum(float((a_ - b_).double().pow(2).sum()) for a_, b_ in zip(gs, stale_g))
+                    den = sum(float(a_.double().pow(2).sum()) for a_ in gs)
+                    stale_gd.append((num / den) ** 0.5)
+                if k + 1 < len(draws):                 # the next step's loss and gradients if this update were ignored (stale weights)
+                    cur_draw["idx"], cur_draw["noise"] = draws[k + 1]
+                    loss_st, ld_st = loss_fn(model.model, model.denoiser, model.conditioner, z, tb, model.first_stage_model, model.scale_factor)
+                    stale_g = [g_.detach().clone() for g_ in torch.autograd.grad(loss_st, params)]
+                    stale.append(float(ld_st["loss/full_loss"]))
+                opt.step()
+                dp = [p_.detach() - q_ for p_, q_ in zip(params, p0)]
+                for kk, v in ld.items():
+                    out[f"g15c_{k + 1}_" + kk.replace("/", "_")] = np.array([float(v)])
+                full.append(float(ld["loss/full_loss"]))
+                out[f"g15c_{k + 1}_grad_stats"] = np.stack([stats(g_) for g_ in gs])
+                if k > 0:                                      # (step 1's gradient is G14's g14_diff, asserted above)
+                    out[f"g15c_{k + 1}_grad_sub"] = np.stack([np.pad(gsub(g_, G15C_GRAD_SUB).numpy(), (0, G15C_GRAD_SUB - gsub(g_, G15C_GRAD_SUB).numel()))
+                                                              for g_ in gs])
+                out[f"g15c_{k + 1}_dp_stats"] = np.stack([stats(d_) for d_ in dp])
+                out[f"g15c_{k + 1}_dp_sub"] = np.stack([np.pad(gsub(d_, G15C_DP_SUB).numpy(), (0, G15C_DP_SUB - gsub(d_, G15C_DP_SUB).numel()))
+                                                        for d_ in dp])
+                print(f"[golden] G15c step {k + 1}: loss {full[-1]:.6f}, lr {opt.param_groups[0]['lr']:.4e} ({time.time() - t0:.1f}s)", flush=True)
+    finally:
+        model.conditioner.forward = real_cond
+        torch.randn_like = real_randn_like
+    print(f"[golden] G15c losses {full}, with the previous update ignored {stale}; gradients with it ignored: rel rms {stale_gd}")
+    for k in range(2):                                  # "update applied" and "update ignored" cannot both pass the checks
+        assert abs(full[k + 1] - stale[k]) >= 3 * G15C_LOSS_TOL * abs(full[k + 1]), (full, stale, G15C_LOSS_TOL)
+        assert stale_gd[k] >= 5 * G15C_GRAD_TOL, (stale_gd, G15C_GRAD_TOL)
+    out["g15c_loss_update_ignored"] = np.array(stale)
+    cond = recorded["cond"]                                           # (G14's conditioning: not stored again)
+    assert np.array_equal(cond["concat"].detach().numpy(), g14["g14_c_concat"]) and np.array_equal(cond["t_crossattn"].detach().numpy(),
+                                                                                                  g14["g14_c_txt"])
+    out.update({"g15c_z": z.numpy(), "g15c_sigma_idx": torch.stack([d[0] for d in draws]).numpy(),
+                "g15c_noise": torch.stack([d[1] for d in draws]).numpy(), "g15c_names": np.array(names),
+                "g15c_lr": np.array([G15C_LR]), "g15c_eps": np.array([G15C_EPS]), "g15c_weight_decay": np.array([G15C_WD])})
+    np.savez_compressed(os.path.join(HERE, "iterated_golden.npz"), **out)
+    print(f"[golden] G15 done ({time.time() - t0:.1f}s)")
+
+
+def main(only_g11: bool = False, only_g12: bool = False, only_g13: bool = False, only_g14: bool = False, only_g15: bool = False):
     t0 = time.time()
     torch.set_grad_enabled(False)
     import_reference()
@@ -425,6 +632,9 @@ def main(only_g11: bool = False, only_g12: bool = False, only_g13: bool = False,
     if only_g14:
         g14(model, t0)
         return
+    if only_g15:
+        g15(model, S, t0)
+        return
     sampler = S.EulerEDMSampler(
         num_steps=10,
         discretization_config={"target": "sgm.modules.diffusionmodules.discretizer.LegacyDDPMDiscretization"},
@@ -541,6 +751,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--g14" in sys.argv:
         main(only_g14=True)
+        sys.exit(0)
+    if "--g15" in sys.argv:
+        main(only_g15=True)
         sys.exit(0)
     main(only_g11="--g11" in sys.argv, only_g12="--g12" in sys.argv)
     if "--all" in sys.argv:

@@ -371,9 +371,12 @@ def test_reverse_pass_at_512_vs_oracle_autograd(engine, env):
     _check("reverse pass at 64x64 latents (dense map cotangents) vs oracle autograd", got, ref, 3e-2)
 
 
-def test_sampling_with_attend_and_excite_runs_and_lowers_the_local_loss(engine, env):
+def test_sampling_with_attend_and_excite_runs_the_scheduled_updates(engine, env):
     """aae_enabled: True through the sampler (reference sampling.py:355-420): finite latent, one local loss and one decoded
-    intermediate per step, and the iterated updates at the scheduled steps push the loss DOWN relative to the plain trajectory"""
+    intermediate per step, a trajectory that differs from the plain one, and the scheduled number of gradient evaluations: of the
+    8 steps only i = 5 is in iter_lst (5, 9, ..., 25) — thres -0.5, which the local loss (about -1/12 on these nearly uniform maps) does
+    not reach, so 1 + max_iter = 21 updates there and one at each of the 7 others.  (The loop's exits and the schedule against the
+    reference: tests/test_iterated_gpu.py)"""
     from udifftext_amd import config as C, pipeline
     dev = env.dev
     batch = env.synth.synthetic_batch(1, 128, 128, 4, seed=14)
@@ -384,8 +387,11 @@ def test_sampling_with_attend_and_excite_runs_and_lowers_the_local_loss(engine, 
     cfgs = C.default_runtime_config(steps=8, batch_size=1, noise_iters=0)
     torch.manual_seed(5)
     x0 = sampler.get_init_noise(cfgs, engine, cond=c, batch=batch, uc=uc)
+    evals0 = getattr(sampler, "aae_evaluations", 0)
     z = sampler(engine, x0.clone(), cond=c, batch=batch, uc=uc, aae_enabled=True)
     assert bool(torch.isfinite(z).all()) and len(sampler.last_local_losses) == 8 and len(sampler.last_inters) == 8
+    assert max(sampler.last_local_losses) > -0.5
+    assert sampler.aae_evaluations - evals0 == 7 + 21 and sampler.last_aae_stats == "28 gradient evaluations"
     assert sampler.last_inters[0].shape == (128, 128, 3)
     z_plain = sampler(engine, x0.clone(), cond=c, batch=batch, uc=uc, aae_enabled=False)
     assert not torch.equal(z, z_plain)

@@ -42,13 +42,13 @@ def _bf(t):
 @pytest.fixture(scope="module")
 def env(cuda):
     import udifftext_amd  # noqa: F401
-    from udifftext_amd import lib, ops, training
+    from udifftext_amd import backward, lib, ops, training
     assert lib.load().udt_device_arch_ok() == 1
     torch.set_grad_enabled(False)
 
     class Env:
         pass
-    Env.ops, Env.training, Env.dev = ops, training, cuda
+    Env.ops, Env.training, Env.bw, Env.dev = ops, training, backward, cuda
     return Env
 
 
@@ -286,7 +286,8 @@ def test_training_gradients_at_512_vs_oracle_autograd(engine, env):
 
 def test_training_step_updates_only_the_trained_parameters(engine, env):
     """training.training_step: gradients -> AdamW on the t_attn / t_norm masters; every other parameter untouched; the packed layouts
-    and the graph fingerprint notice; the same step from the same state is bit-reproducible"""
+    and the graph fingerprint notice — the second step's loss through the warm caches equals the same loss from cold caches bit for
+    bit; the same step from the same state is bit-reproducible"""
     import copy
     from aae_fixture import train_batch
     from sgm.modules.diffusionmodules.sampling import weights_fingerprint
@@ -316,8 +317,20 @@ def test_training_step_updates_only_the_trained_parameters(engine, env):
         assert not torch.equal(p.detach(), before[n]) or float(grads[n].abs().max()) == 0.0, n
     for n, p in list(engine.model.named_parameters())[:6]:
         assert torch.equal(p.detach(), other[n])
+    # the step-2 loss through the caches step 1 left behind must equal the same loss from COLD caches (every packed layout of the
+    # forward, the backward layouts, the time-embedding rows rebuilt from the masters): bit for bit — same kernels, same inputs
+    ld2w, _ = tr.training_loss_and_grads(engine, z, cond, seg, segm, sigma_idx=idx, noise=noise, want_grads=False)
+    for m in engine.modules():
+        for a in ("_pk_key", "_pk8_key", "_pkln_key", "_pkln8_key", "_pkfp_key") + (("_emb_key",) if hasattr(m, "_emb_w") else ()):
+            if getattr(m, a, None) is not None:
+                setattr(m, a, None)
+    env.bw.clear_cache()
+    ld2c, _ = tr.training_loss_and_grads(engine, z, cond, seg, segm, sigma_idx=idx, noise=noise, want_grads=False)
+    for k in ("loss/diff_loss", "loss/full_loss"):
+        assert torch.equal(ld2w[k], ld2c[k]), (k, float(ld2w[k]), float(ld2c[k]))
     ld2 = tr.training_step(engine, opt, z, cond, seg, segm, sigma_idx=idx, noise=noise)
     assert float(ld2["loss/full_loss"]) != float(ld1["loss/full_loss"])          # the second step sees the updated weights
+    assert torch.equal(ld2["loss/full_loss"], ld2w["loss/full_loss"])
     with torch.no_grad():                                                          # restore the engine for the other tests
         for n, p in named:
             p.copy_(before[n])

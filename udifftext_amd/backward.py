@@ -18,6 +18,7 @@ torch is used for memory only (allocation, views, channel concatenation / split,
 """
 from __future__ import annotations
 
+import weakref
 from typing import Callable, List, Optional, Tuple
 
 import torch
@@ -28,17 +29,23 @@ from . import ops, packing
 Bwd = Callable[[Optional[torch.Tensor]], Optional[torch.Tensor]]
 DEBUG_SUMS: Optional[list] = None       # (tools/debug_train3.py: per-layer checksums of the tape-mode forward)
 
-_CACHE: dict = {}
+# the backward layouts (W^T of every linear, the flipped 3x3 taps, the fused wqkvT) of each module: {module: {tag: (key, layout)}}.
+# Keyed by the module object itself, weakly: a freed engine's layouts die with it, and a new module that happens to get the same
+# id() (and weights at reused pointers with equal version counts) cannot hit them.  Validated like _Packed.packed() by _key()
+# (data_ptr, _version, device); writes through ``p.data`` do not bump _version, so neither cache sees them.
+_CACHE: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
 def _cached(mod, tag: str, build):
-    key = (id(mod), tag)
     ver = mod._key()
-    hit = _CACHE.get(key)
+    per_mod = _CACHE.get(mod)
+    if per_mod is None:
+        per_mod = _CACHE[mod] = {}
+    hit = per_mod.get(tag)
     if hit is None or hit[0] != ver:
         with torch.no_grad():
             hit = (ver, build())
-        _CACHE[key] = hit
+        per_mod[tag] = hit
     return hit[1]
 
 
@@ -55,9 +62,13 @@ def _need_masters(mod) -> None:
 # ------------------------------------------------------------------------------------------------ linear / convolution
 def linear_bwd(lin, dy: torch.Tensor, add: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dX = dY W (+ add): the forward GEMM on W^T packed as [in_features, out_features]"""
+    return ops.linear(dy, _linear_wt(lin), None, residual=add)
+
+
+def _linear_wt(lin) -> torch.Tensor:
+    """backward-data weights of a linear: W^T packed as [in_features, out_features]"""
     _need_masters(lin)
-    wt = _cached(lin, "wT", lambda: packing.pack_linear(lin.weight.detach().t().contiguous()))
-    return ops.linear(dy, wt, None, residual=add)
+    return _cached(lin, "wT", lambda: packing.pack_linear(lin.weight.detach().t().contiguous()))
 
 
 def _conv_wt(conv, n_pad: int = 4) -> torch.Tensor:

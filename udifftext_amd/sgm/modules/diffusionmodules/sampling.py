@@ -99,7 +99,8 @@ def _all_zero(t: torch.Tensor) -> bool:
 def weights_fingerprint(model) -> int:
     """changes whenever a parameter of ``model`` is re-assigned, moved or written in place (load_state_dict,
     init_from_ckpt, .to()): captured hipGraphs bake in the device pointers of the packed weights, so the graph caches
-    are keyed by it (~1 ms for the engine's 1330 tensors, once per sampling call)"""
+    are keyed by it (~1 ms for the engine's 1330 tensors, once per sampling call).  Writes through ``p.data``
+    (``p.data.copy_()``, EMA swaps) do not bump ``_version`` and are not seen."""
     h = 0
     for p in model.parameters():
         h = (h * 1000003 + p._version * 8191 + p.data_ptr()) & 0xFFFFFFFFFFFFFFFF
@@ -518,7 +519,7 @@ class EulerEDMSampler(EDMSampler):
         stepper.check()
         print(f"Local losses: {local_losses}")
         self.last_local_losses, self.last_inters = local_losses, inters
-        self.last_aae_stats = f"{self.aae_evaluations - evals0} gradient evaluations"
+        self.last_aae_stats = f"{getattr(self, 'aae_evaluations', 0) - evals0} gradient evaluations"
         try:
             import imageio
             os.makedirs("./temp/inters", exist_ok=True)

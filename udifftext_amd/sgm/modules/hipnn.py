@@ -119,7 +119,8 @@ class _Packed(nn.Module):
     """mixin: cache of repacked device weights, invalidated when parameters move or change.
     ``fused_children()``: child modules whose weights this module's ``_pack`` consumes (fused q|k|v, ...) — they are never
     evaluated on their own, so load-time ``prepare`` does not pack them separately.  After ``prepare(free_masters=True)``
-    the cache is frozen (``_pk_frozen``): the fp32 masters are gone and ``packed()`` never looks at them again."""
+    the cache is frozen (``_pk_frozen``): the fp32 masters are gone and ``packed()`` never looks at them again.
+    Writes through ``p.data`` (``p.data.copy_()``, EMA swaps) do not bump ``_version``: the cache does not see them."""
 
     def _key(self):
         ps = list(self.parameters(recurse=False))
