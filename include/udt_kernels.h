@@ -34,6 +34,8 @@
  *                       denoiser_scaling.py:16-22, sampling_utils.py:8-9,39-40, sampling.py:85-86,348-351
  *   udt_cfg_sampler_step  the same CFG denoise + the update of HeunEDMSampler, EulerAncestralSampler,
  *                       DPMPP2SAncestralSampler, DPMPP2MSampler (sampling.py:140-215,423-567) as one affine form
+ *   udt_cfg_multistep_step  the same CFG denoise + the update of LinearMultistepSampler (sampling.py:180-215): to_d and
+ *                       the linear multistep sum over up to 8 derivatives
  *   udt_posterior_sample  DiagonalGaussianDistribution.sample  sgm/modules/distributions/distributions.py:24-41
  *   udt_nchw_to_nhwc / udt_nhwc_to_nchw   layout change at the NCHW fp32 plugin boundary
  *                       (rearrange "b c h w -> b (h w) c", sgm/modules/attention.py:405,412)
@@ -397,6 +399,24 @@ typedef struct {
 int udt_cfg_sampler_step(const float* xin, const float* eps, const float* aux, const float* prev, const float* noise,
                          float* xout, float* denoised_out, int32_t B, int32_t hw, int32_t ld_eps, udt_sampler_coefs k,
                          void* stream);
+/* CFG linear-multistep step (one launch per UNet evaluation of LinearMultistepSampler):
+ *   den   = den_u + scale*(den_c - den_u),  den_{u,c} = xin + c_out*eps_{u,c}     (c_out = -quantised sigma)
+ *   d     = (xin - den) / sigma                                                  (unquantised sigma: to_d)
+ *   xout  = xin + (k[0]*d + k[1]*hist[1] + ... + k[n-1]*hist[n-1])               (summed in this order)
+ *   d_out = d
+ * eps fp32 [2B, hw, ld_eps] (uncond half first, 16-byte aligned); xin, hist[1..n-1], xout, d_out fp32 NCHW [B,4,h,w].
+ * hist[j] is the derivative of j evaluations ago (hist[0] is unused); k[] are the quadrature coefficients of
+ * sampling_utils.linear_multistep_coeff, computed on the host in float64 and rounded.  1 <= n <= UDT_MULTISTEP_MAX.
+ * xout may alias xin; d_out aliases none of xin, xout and hist[1..n-1]. */
+#define UDT_MULTISTEP_MAX 8
+typedef struct {
+  float c_out, scale, sigma;
+  int32_t n;
+  float k[UDT_MULTISTEP_MAX];
+  const float* hist[UDT_MULTISTEP_MAX];
+} udt_multistep_coefs;
+int udt_cfg_multistep_step(const float* xin, const float* eps, float* xout, float* d_out, int32_t B, int32_t hw,
+                           int32_t ld_eps, udt_multistep_coefs k, void* stream);
 /* z = scale * (mean + exp(0.5*clamp(logvar,-30,20)) * noise); moments fp32 [B, hw, ldm] NHWC (mean ch 0..3,
  * logvar ch 4..7), noise fp32 NCHW [B,4,h,w], z fp32 NCHW [B,4,h,w]. */
 int udt_posterior_sample(const float* moments, const float* noise, float* z, int32_t B, int32_t hw, int32_t ldm,

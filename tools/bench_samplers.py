@@ -5,7 +5,8 @@
 
 One JSON line per configuration on stdout (``name``, ``sampler``, ``sampler_steps``, ``unet_evaluations``, ``images_per_s``).
 Euler 50 is bench.py's ``value`` measured the same way.  For the step kernel's time per launch run one configuration under
-``rocprofv3 --kernel-trace --stats`` and read ``cfg_sampler_kernel`` from the stats file.
+``rocprofv3 --kernel-trace --stats`` and read ``cfg_sampler_kernel`` (``cfg_multistep_kernel`` for linear_multistep) from the
+stats file.
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 CONFIGS = {"euler_50": ("euler", 50), "dpmpp2m_20": ("dpmpp2m", 20), "euler_a_20": ("euler_a", 20), "heun_10": ("heun", 10),
-           "dpmpp2s_a_10": ("dpmpp2s_a", 10)}
+           "dpmpp2s_a_10": ("dpmpp2s_a", 10), "linear_multistep_20": ("linear_multistep", 20)}
 
 
 def main():

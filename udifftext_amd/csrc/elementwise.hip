@@ -4,6 +4,7 @@
 //                                         sampling_utils.py:8-9,39-40, sampling.py:85-86,348-351
 //   udt_cfg_sampler_step                : the same CFG denoise + the update of any sampler of sampling.py:140-215,423-567
 //                                         as one affine form (host coefficients: udifftext_amd/sgm/.../sampling.py)
+//   udt_cfg_multistep_step              : the same CFG denoise + LinearMultistepSampler's update, sampling.py:180-215
 //   udt_posterior_sample                : distributions.py:24-41 (+ LatentEncoder scale, encoders/modules.py:1011-1014)
 //   udt_embed_tokens                    : encoders/modules.py:1069-1085,1160-1163
 //   udt_timestep_embedding              : diffusionmodules/util.py:206-230
@@ -73,6 +74,45 @@ __global__ void cfg_sampler_kernel(const float* xin, const float* __restrict__ e
     if (noise) acc += k.kn * noise[o];
     xout[o] = acc;
     if (den_out) den_out[o] = den;
+  }
+}
+
+// CFG linear-multistep step: den as in cfg_euler_kernel, d = (xin - den)/sigma, then
+//   xout = xin + (k[0]*d + k[1]*hist[1] + ... + k[n-1]*hist[n-1])   (summed in this order),  d_out = d.
+// xout may alias xin (each thread reads its pixel's inputs before it writes); d_out aliases none of the others.
+// Every load of the thread is issued before the first use: the history slots are guarded by the uniform bound n and
+// unrolled over the 8 slots, so hist[] is only indexed by constants and its loads overlap instead of queueing per slot.
+__global__ void cfg_multistep_kernel(const float* xin, const float* __restrict__ eps, float* xout,
+                                     float* __restrict__ d_out, int B, int hw, int ld, udt_multistep_coefs k) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * hw) return;
+  const int b = i / hw;
+  const int pix = i - b * hw;
+  const f32x4 eu = *reinterpret_cast<const f32x4*>(eps + ((long long)b * hw + pix) * ld);
+  const f32x4 ec = *reinterpret_cast<const f32x4*>(eps + ((long long)(b + B) * hw + pix) * ld);
+  const long long base = (long long)b * 4 * hw + pix;
+  float xv[4], hv[UDT_MULTISTEP_MAX][4] = {};
+#pragma unroll
+  for (int c = 0; c < 4; ++c) xv[c] = xin[base + (long long)c * hw];
+#pragma unroll
+  for (int j = 1; j < UDT_MULTISTEP_MAX; ++j)
+    if (j < k.n) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) hv[j][c] = k.hist[j][base + (long long)c * hw];
+    }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const long long o = base + (long long)c * hw;
+    const float du = eu[c] * k.c_out + xv[c];
+    const float dc = ec[c] * k.c_out + xv[c];
+    const float den = du + k.scale * (dc - du);
+    const float d = (xv[c] - den) / k.sigma;          // to_d, sampling_utils.py:39-40
+    float acc = k.k[0] * d;
+#pragma unroll
+    for (int j = 1; j < UDT_MULTISTEP_MAX; ++j)
+      if (j < k.n) acc += k.k[j] * hv[j][c];
+    xout[o] = xv[c] + acc;                            // sampling.py:212
+    d_out[o] = d;
   }
 }
 
@@ -299,6 +339,24 @@ extern "C" int udt_cfg_sampler_step(const float* xin, const float* eps, const fl
   UDT_STREAM;
   hipLaunchKernelGGL(cfg_sampler_kernel, dim3(nblk((long long)B * hw)), dim3(256), 0, s, xin, eps, aux, prev, noise, xout,
                      denoised_out, B, hw, ld_eps, k);
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}
+
+extern "C" int udt_cfg_multistep_step(const float* xin, const float* eps, float* xout, float* d_out, int32_t B,
+                                      int32_t hw, int32_t ld_eps, udt_multistep_coefs k, void* stream) {
+  if (!xin || !eps || !xout || !d_out) return UDT_ERR_BAD_ARG;
+  if (k.n < 1 || k.n > UDT_MULTISTEP_MAX) return UDT_ERR_BAD_ARG;
+  if (B <= 0 || hw <= 0 || ld_eps < 4 || ld_eps % 4 != 0 || (long long)B * hw > 0x7fffffffLL || k.sigma == 0.f)
+    return UDT_ERR_BAD_SHAPE;
+  if (reinterpret_cast<uintptr_t>(eps) % 16 != 0) return UDT_ERR_BAD_SHAPE;
+  // d_out is written while xin and the history are read by other threads: it may alias none of them (nor xout)
+  if (d_out == xin || d_out == xout) return UDT_ERR_BAD_ARG;
+  for (int j = 1; j < k.n; ++j)
+    if (!k.hist[j] || k.hist[j] == d_out) return UDT_ERR_BAD_ARG;
+  UDT_STREAM;
+  hipLaunchKernelGGL(cfg_multistep_kernel, dim3(nblk((long long)B * hw)), dim3(256), 0, s, xin, eps, xout, d_out, B, hw,
+                     ld_eps, k);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
 }

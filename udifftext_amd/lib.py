@@ -50,6 +50,15 @@ class SamplerCoefs(C.Structure):
                 ("c_out", C.c_float), ("scale", C.c_float)]
 
 
+MULTISTEP_MAX = 8                                    # UDT_MULTISTEP_MAX
+
+
+class MultistepCoefs(C.Structure):
+    """udt_multistep_coefs (by value): d = (xin - den)/sigma; xout = xin + (k[0]*d + k[1]*hist[1] + ... + k[n-1]*hist[n-1])"""
+    _fields_ = [("c_out", C.c_float), ("scale", C.c_float), ("sigma", C.c_float), ("n", C.c_int32),
+                ("k", C.c_float * MULTISTEP_MAX), ("hist", C.c_void_p * MULTISTEP_MAX)]
+
+
 # every symbol include/udt_kernels.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _fp = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p
 SYMBOLS = {
@@ -105,6 +114,7 @@ SYMBOLS = {
     "udt_unet_input": (C.c_int, [_fp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "udt_cfg_euler_step": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
     "udt_cfg_sampler_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, SamplerCoefs, _vp]),
+    "udt_cfg_multistep_step": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, MultistepCoefs, _vp]),
     "udt_sampler_step": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
     "udt_posterior_sample": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _vp]),
     "udt_nchw_to_nhwc": (C.c_int, [_fp, _vp, _i32, _i32, _i64, _i32, _f32, _vp]),

@@ -9,7 +9,7 @@ import contextlib
 import ctypes as C
 import os
 import threading
-from typing import NamedTuple, Optional
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -776,6 +776,31 @@ def cfg_sampler_step(xin: torch.Tensor, eps: torch.Tensor, c_out: float, scale: 
     k = L.SamplerCoefs(kx, kd, ka, kp, kn, c_out, scale)
     L.check(L.load().udt_cfg_sampler_step(_ptr(xin), _ptr(eps), _ptr(aux), _ptr(prev), _ptr(noise), _ptr(out), _ptr(denoised),
                                           B, h * w, eps.shape[-1], k, _stream()), "udt_cfg_sampler_step")
+    return out
+
+
+def cfg_multistep_step(xin: torch.Tensor, eps: torch.Tensor, c_out: float, scale: float, sigma: float, coefs: Sequence[float],
+                       hist: Sequence[torch.Tensor] = (), d_out: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """one launch of udt_cfg_multistep_step: den = CFG(xin + c_out*eps_u, xin + c_out*eps_c); d = (xin - den)/sigma;
+    out = xin + (coefs[0]*d + coefs[1]*hist[0] + ... + coefs[n-1]*hist[n-2]) (hist: the older derivatives, newest first);
+    d_out <- d.  xin / hist / out / d_out: fp32 NCHW [B,4,h,w] contiguous; out defaults to xin (in place); d_out is required and
+    aliases none of the others."""
+    B, _, h, w = xin.shape
+    out = xin if out is None else out
+    n = len(coefs)
+    assert 1 <= n <= L.MULTISTEP_MAX and len(hist) == n - 1, "n = len(coefs) in 1..8 and len(hist) = n - 1"
+    assert d_out is not None, "d_out is required"
+    for t in (xin, out, d_out, *hist):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, 4, h, w), "fp32 NCHW [B,4,h,w]"
+    assert eps.dtype == torch.float32 and eps.is_contiguous() and tuple(eps.shape[:-1]) == (2 * B, h, w) and eps.shape[-1] >= 4
+    k = L.MultistepCoefs(c_out, scale, sigma, n)
+    for j, c in enumerate(coefs):
+        k.k[j] = c
+    for j, t in enumerate(hist):
+        k.hist[j + 1] = _ptr(t)
+    L.check(L.load().udt_cfg_multistep_step(_ptr(xin), _ptr(eps), _ptr(out), _ptr(d_out), B, h * w, eps.shape[-1], k,
+                                            _stream()), "udt_cfg_multistep_step")
     return out
 
 

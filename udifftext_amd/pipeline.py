@@ -44,13 +44,14 @@ SAMPLERS = {
     "heun": "HeunEDMSampler",
     "euler_a": "EulerAncestralSampler",
     "dpmpp2s_a": "DPMPP2SAncestralSampler",
+    "linear_multistep": "LinearMultistepSampler",
 }
 
 
 def init_sampling(steps: int, scale: float, device: torch.device, verbose: bool = False, sampler: str = "euler"):
     """reference util.py:24-47: EulerEDMSampler + LegacyDDPMDiscretization + VanillaCFG(scale).  ``sampler`` picks another
     sampler of the reference's sampling.py with the same discretization and guider (SAMPLERS; their default parameters:
-    eta = s_noise = 1 for the ancestral ones, s_churn = 0 for Heun)"""
+    eta = s_noise = 1 for the ancestral ones, s_churn = 0 for Heun, order = 4 for linear_multistep)"""
     from sgm.modules.diffusionmodules import sampling as S
     if sampler not in SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}; one of {sorted(SAMPLERS)}")

@@ -14,7 +14,8 @@ out of scope and raise.
 
 HeunEDMSampler, EulerAncestralSampler, DPMPP2SAncestralSampler and DPMPP2MSampler (reference :140-215, :423-567) run the
 same UNet call followed by ONE udt_cfg_sampler_step launch per evaluation; each supplies a per-step plan of host
-coefficients (``Eval``, bottom of this file).
+coefficients (``Eval``, bottom of this file).  LinearMultistepSampler (reference :180-215) ends every evaluation in
+ONE udt_cfg_multistep_step launch instead (``MultistepEval``: to_d and the sum over a ring of derivative buffers).
 """
 from __future__ import annotations
 
@@ -194,12 +195,16 @@ class _Stepper:
         ops.cfg_euler_step(x, eps, sigma, sigma_next, self.scale, denoised=denoised, c_out=-sq)
 
     def run_plan(self, bufs: Dict[str, torch.Tensor], plan, noise: Optional[torch.Tensor] = None) -> None:
-        """one step of a non-Euler sampler: per evaluation of ``plan`` (a tuple of ``Eval``), the UNet call on its source buffer
-        and one udt_cfg_sampler_step launch; ``bufs`` maps the plan's buffer names to fp32 NCHW tensors, ``noise`` is this
-        step's ancestral draw"""
+        """one step of a non-Euler sampler: per evaluation of ``plan`` (a tuple of ``Eval`` / ``MultistepEval``), the UNet call on
+        its source buffer and one udt_cfg_sampler_step / udt_cfg_multistep_step launch; ``bufs`` maps the plan's buffer names to
+        fp32 NCHW tensors, ``noise`` is this step's ancestral draw"""
         for e in plan:
             src = bufs[e.src]
             eps, sq = self.unet_eps(src, e.sigma)
+            if isinstance(e, MultistepEval):
+                ops.cfg_multistep_step(src, eps, -sq, self.scale, e.sigma, (e.k0,) + tuple(k for _, k in e.hist),
+                                       hist=[bufs[b] for b, _ in e.hist], d_out=bufs[e.d_out], out=bufs[e.out])
+                continue
             ops.cfg_sampler_step(src, eps, -sq, self.scale, e.kx, e.kd,
                                  aux=bufs[e.aux] if e.aux else None, ka=e.ka,
                                  prev=bufs[e.prev] if e.prev else None, kp=e.kp,
@@ -708,6 +713,30 @@ class Eval(NamedTuple):
     den_out: Optional[str] = None
 
 
+class MultistepEval(NamedTuple):
+    """one UNet evaluation + the fused linear-multistep update (udt_cfg_multistep_step): d = (src - den(src, sigma))/sigma;
+    out = src + (k0*d + k_1*hist_1 + ...) over ``hist`` = ((buffer, k), ...), the older derivatives newest first; d_out <- d"""
+    sigma: float                       # UNQUANTISED sigma (to_d); c_in, c_out and the timestep use its quantised value
+    src: str
+    out: str
+    d_out: str
+    k0: float
+    hist: tuple = ()
+
+
+def plan_buffers(plans) -> list:
+    """the names of the buffers ``plans`` ((step, plan) pairs) read or write, besides the latent "x", in first-use order"""
+    names = []
+    for _, plan in plans:
+        for e in plan:
+            if isinstance(e, MultistepEval):
+                used = (e.src, e.out, e.d_out) + tuple(b for b, _ in e.hist)
+            else:
+                used = (e.src, e.out, e.aux, e.prev, e.den_out)
+            names.extend(b for b in used if b and b != "x" and b not in names)
+    return names
+
+
 def ancestral_step(sigma: float, sigma_next: float, eta: float):
     """reference sampling_utils.get_ancestral_step in float64 -> (sigma_down, sigma_up)"""
     if not eta:
@@ -724,7 +753,8 @@ def _euler_to(sigma: float, target: float):
 
 class _GraphedPlan(_GraphedSteps):
     """hipGraph replay of a plan-driven sampler: one graph per (step index, plan); besides the latent, the scratch / history
-    buffers and the run's ancestral noise ([steps, B, 4, h, w], refreshed per run) are static"""
+    buffers and the run's ancestral noise ([steps, B, 4, h, w], refreshed per run) are static.  Buffers a plan names beyond
+    "t" / "h0" / "h1" are allocated before its capture"""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -740,6 +770,9 @@ class _GraphedPlan(_GraphedSteps):
 
     def capture_plan(self, i: int, plan) -> None:
         st = self.st
+        for name in plan_buffers([(i, plan)]):              # e.g. LinearMultistepSampler's derivative ring d0 .. d{order-1}
+            if name not in self.bufs:
+                self.bufs[name] = torch.zeros_like(self.x)
         for e in plan:
             st.emb_rows(st.quantise(e.sigma)[0])             # time-embedding rows are cached outside the graph
         if not self.warm:
@@ -818,6 +851,8 @@ class _PlanSampler:
                 return out
         stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale)
         bufs = {"x": x, "t": torch.empty_like(x), "h0": torch.empty_like(x), "h1": torch.empty_like(x)}
+        for name in plan_buffers(plans):
+            bufs.setdefault(name, torch.empty_like(x))
         for i, plan in plans:
             stepper.run_plan(bufs, plan, noise[i - init_step] if noise is not None else None)
         stepper.check()
@@ -1030,3 +1065,51 @@ class DPMPP2MSampler(_PlanSampler, BaseDiffusionSampler):
         r = (t - (-np.log(float(sig[i - 1])))) / h
         m3, m4 = 1.0 + 1.0 / (2.0 * r), 1.0 / (2.0 * r)
         return (Eval(s, "x", "x", kx=m1, kd=-m2 * m3, prev=old, kp=m2 * m4, den_out=hist),)
+
+
+MULTISTEP_MAX_ORDER = 8                                  # udt_multistep_coefs holds 8 terms (UDT_MULTISTEP_MAX)
+
+
+def linear_multistep_coeff(order: int, t, i: int, j: int) -> float:
+    """reference sampling_utils.linear_multistep_coeff: the integral over [t[i], t[i+1]] of the Lagrange basis polynomial of node
+    t[i-j] on the nodes t[i], ..., t[i-order+1] — integrated exactly, in closed form, in float64 (the reference calls
+    scipy.integrate.quad, which is exact for these polynomials up to rounding).  The variable is shifted by t[i] so that the
+    polynomial's coefficients stay on the scale of the step."""
+    if order - 1 > i:
+        raise ValueError(f"Order {order} too high for step {i}")
+    t = np.asarray(t, dtype=np.float64)
+    a = t[i]
+    others = [k for k in range(order) if k != j]
+    p = np.polynomial.polynomial.polyfromroots([t[i - k] - a for k in others]) if others else np.array([1.0])
+    den = float(np.prod([t[i - j] - t[i - k] for k in others]))
+    q = np.polynomial.polynomial.polyint(p)                # q(0) = 0
+    return float(np.polynomial.polynomial.polyval(t[i + 1] - a, q) / den)
+
+
+class LinearMultistepSampler(_PlanSampler, BaseDiffusionSampler):
+    """reference sampling.py:180-215: the linear multistep method over the last ``order`` derivatives d = to_d(x, sigma, den) —
+    1 evaluation per step.  Step i uses cur_order = min(i - init_step + 1, order) terms with linear_multistep_coeff weights
+    computed on the host from the fp32 schedule; the derivatives live in a ring of ``order`` static buffers d{i % order}, and
+    every evaluation ends in one udt_cfg_multistep_step launch.  Draws no noise.
+
+    REFERENCE QUIRK (not copied): the reference's __call__ calls its first argument as a bare denoiser,
+    ``denoiser(*guider.prepare_inputs(x, sigma, cond, uc), **kwargs)``, and forwards every other keyword (init_step included)
+    into that call — unlike its other samplers, which take the engine.  Here, as for the other samplers, the first argument is
+    the engine and init_step starts the loop at step init_step with an empty history."""
+
+    def __init__(self, order=4, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.order = order
+
+    def _check_fast_path(self):
+        super()._check_fast_path()
+        if not 1 <= int(self.order) <= MULTISTEP_MAX_ORDER:
+            raise NotImplementedError(f"LinearMultistepSampler order {self.order}: the fused step (udt_cfg_multistep_step) "
+                                      f"holds 1..{MULTISTEP_MAX_ORDER} derivatives")
+
+    def step_plan(self, sig, i, init_step=0):
+        order = int(self.order)
+        cur = min(i - init_step + 1, order)
+        ks = [linear_multistep_coeff(cur, sig, i, j) for j in range(cur)]
+        slot = lambda m: f"d{m % order}"
+        return (MultistepEval(float(sig[i]), "x", "x", slot(i), ks[0], tuple((slot(i - j), ks[j]) for j in range(1, cur))),)
