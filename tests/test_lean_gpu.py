@@ -326,6 +326,69 @@ def test_conv3x3_with_four_output_channels_fp32(env, cuda, case):
         env.reset()
 
 
+def test_conv_n4_guard_declines_what_its_kernel_does_not_implement(env, cuda):
+    """conv_n4_applies (gemm.hip) sees the descriptor before udt_gemm's own validation.  From an accepted problem (the UNet's `out`
+    convolution at 64 x 64, 320 -> 4, fp32) each case changes ONE field the dot-product kernel does not read: the packed K, lda,
+    an MX8-emitting epilogue, the input activation, a weight pitch below K.  The launch must then either be refused (UDT_ERR_BAD_*) or
+    give the general path's result — the general path (conv_n4 switched off) is asked first: when it refuses, so must conv_n4's.
+    (lda of a convolution: the gathered path addresses the NHWC input by pixel and C1 and never reads lda; 0 and C1 are the values a
+    caller may pass.)"""
+    import ctypes as C
+    from udifftext_amd import lib as L
+    lib = L.load()
+    B, H, W, Cin = 1, 64, 64, 320
+    g = torch.Generator(device="cpu").manual_seed(77)
+    x = torch.randn((B, H, W, Cin), generator=g).to(cuda).bfloat16()
+    w4 = (torch.randn((4, Cin, 3, 3), generator=g) / math.sqrt(9 * Cin)).to(cuda)
+    b = torch.randn((4,), generator=g).to(cuda)
+    y = F.conv2d(x.float().permute(0, 3, 1, 2), w4.bfloat16().float(), b, padding=1).permute(0, 2, 3, 1)
+    K = 9 * Cin
+    wbuf = torch.zeros((4, K + 64), dtype=torch.bfloat16, device=cuda)      # room for the K + 64 case (ldw = K + 64 rows)
+    q8 = torch.zeros((B * H * W, 64), dtype=torch.uint8, device=cuda)
+    q8s = torch.zeros((1, B * H * W), dtype=torch.int32, device=cuda)
+    ws = torch.zeros(env.ops.WORKSPACE_BYTES, dtype=torch.uint8, device=cuda)
+
+    def launch(**change):
+        out = torch.full((B, H, W, 4), float("nan"), dtype=torch.float32, device=cuda)
+        kk = change.pop("K", K)
+        wv = wbuf.view(-1)[:4 * kk].view(4, kk)
+        wv.zero_()
+        wv[:, :K] = env.packing.pack_conv(w4)
+        d = env.ops.gemm_desc(a=x.data_ptr(), w=wv.data_ptr(), bias=b.data_ptr(), out=out.data_ptr(), M=B * H * W, N=4, K=kk, lda=0,
+                              ldo=4, Hin=H, Win=W, C1=Cin, C2=0, Hout=H, Wout=W, ksize=3, stride=1, pad_t=1, pad_l=1,
+                              rows_per_batch=H * W, flags=L.GEMM_CONV | L.GEMM_OUT_F32)
+        for k, v in change.items():
+            setattr(d, k, v)
+        rc = lib.udt_gemm(C.byref(d), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return rc, out
+
+    bad = (-1, -2)                                      # UDT_ERR_BAD_SHAPE / UDT_ERR_BAD_ARG
+    cases = {"accepted": {}, "K": {"K": K + 64}, "lda": {"lda": 7 * Cin}, "lda=C1": {"lda": Cin},
+             "q8_out": {"q8_out": q8.data_ptr(), "q8_scale": q8s.data_ptr(), "ld_q8": 64}, "in_act=1": {"in_act": 1},
+             "in_act=2": {"in_act": 2}, "ldw<K": {"ldw": K - 64}}
+    try:
+        for name, change in cases.items():
+            env.dbg("conv_n4", 0)
+            rc0, out0 = launch(**dict(change))
+            env.dbg("conv_n4", 1)
+            rc1, out1 = launch(**dict(change))
+            if rc0 in bad:
+                assert rc1 in bad, f"{name}: the general path refuses this descriptor ({rc0}), conv_n4's guard took it ({rc1})"
+                continue
+            assert rc0 == 0, (name, rc0)
+            assert _rel(out0, y) < REL_RMS, f"{name}: general path {_rel(out0, y):.3e}"
+            if rc1 not in bad:
+                assert rc1 == 0, (name, rc1)
+                e = _rel(out1, y)
+                assert math.isfinite(e) and e < REL_RMS, f"{name}: conv_n4 on gives rel rms {e:.3e} against the convolution"
+        assert cases["accepted"] == {}
+        rc, _ = launch()
+        assert rc == 0
+    finally:
+        env.reset()
+
+
 def test_wide_conv_at_the_16x16_level_with_batches_in_flight(env, cuda):
     """round 6 (UDT_WIDE_LANES_EFF): a launch that shares the device with two other streams (cu_share 3) takes the wide convolution
     already when its tiles fill 3/4 of its share of the CUs — the 16 x 16 level of a UNet call (64 tiles of 256 pixels x 160 channels,

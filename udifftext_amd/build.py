@@ -5,6 +5,7 @@ the repository snapshot to the GPU box.  Re-runs only what is out of date.
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -20,7 +21,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 
 
 def _deps_mtime() -> float:
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm8.h"), os.path.join(CSRC, "conv3p.h"), os.path.join(CSRC, "lean.h"), os.path.join(CSRC, "wide.h"), os.path.join(CSRC, "rowres.h"), os.path.join(CSRC, "tile_common.h"), os.path.join(CSRC, "lean_params.h"), os.path.join(HERE, "..", "include", "udt_kernels.h")]
+    # every header of csrc/ (a hand-kept list missed conv_n4.h: an edit to it left gemm.o stale)
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "udt_kernels.h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -835,7 +835,11 @@ bool conv_n4_applies(const udt_gemm_desc* d) {
     return false;
   if (d->N != 4 || d->C2 != 0 || d->C1 % 64 != 0 || d->C1 > 512 || d->Hout != d->Hin || d->Wout != d->Win || d->ldo % 4 != 0) return false;
   if (d->residual || d->rowvec || d->in_scsh || d->colstats || d->colscale || d->batch > 1 || d->alpha != 1.0f) return false;
-  if ((d->ldw > 0 ? d->ldw : d->K) % 8 != 0) return false;
+  if ((d->ldw > 0 ? d->ldw : d->K) % 8 != 0 || (d->ldw > 0 && d->ldw < d->K)) return false;
+  // (this guard runs before udt_gemm's own validation: everything the kernel does not implement declines here and is refused or
+  //  computed by the general path — the K of the packed taps, an input pitch other than the gathered convolution's C1 (lda 0 = C1),
+  //  an MX8-emitting epilogue, an input activation)
+  if (d->K != 9 * d->C1 || (d->lda != 0 && d->lda != d->C1) || d->q8_out || d->q8_scale || d->rowstat_out || d->in_act != 0) return false;
   if ((reinterpret_cast<uintptr_t>(d->a) | reinterpret_cast<uintptr_t>(d->w) | reinterpret_cast<uintptr_t>(d->out)) & 15) return false;
   return true;
 }
