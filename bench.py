@@ -5,6 +5,11 @@
     python bench.py --size 768 --batch 8 --chars 12                      # BASELINE config #4
     torchrun ... bench.py --gpus 8 --global-batch 64                     # BASELINE config #3 (one sharded global batch)
     python bench.py --steps 2 --warmup 1 --dump-outputs out/             # + the last timed step's frames as out/frames.npy
+    python bench.py --full                                               # + everything measured beside `value` (below)
+
+A plain run does only what `value` needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line.  --full adds, after the timed region, the roofline pass, the other launch modes, the UNet step latency, the
+reference-default workload, the config #5 / #4 passes and the CPU baseline (each --no-* switch drops one of them).
 
 One "step" = one pass of the hot path over one GLOBAL batch of synthetic input.  Default (BASELINE config #2):
 512x512, 50 deterministic Euler (== DDIM eta 0) steps with CFG 5.0, batch 4 per GPU, 9-character labels,
@@ -17,10 +22,10 @@ once per global batch over RCCL.
 
 `value` is the on-config number: every UNet call runs on ONE batch of --batch images (its CFG pair); three such
 batches are in flight per GPU on three launch streams (--in-flight 3, stated in config.workload).  The other launch
-modes (one batch at a time; throughput mode with batches concatenated into larger UNet calls) are reported under
-`images_per_s_by_launch_mode` and are never `value`.
+modes (one batch at a time; throughput mode with batches concatenated into larger UNet calls) are reported by --full
+under `images_per_s_by_launch_mode` and are never `value`.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel class (3x3 convolution); `roofline_classes`
+Prints ONE JSON line (rank 0).  With --full: `roofline` is for the dominant kernel class (3x3 convolution); `roofline_classes`
 adds the GEMM (linears + 1x1 convolutions) and flash-attention classes: algorithmic FLOPs of the launches / their
 summed duration, measured live with HIP events on the launch stream (udt_prof_*) on one extra eager pass of the same
 batch right after the timed region (the timed region replays hipGraphs: no per-launch host calls to bracket).
@@ -64,12 +69,15 @@ def parse():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--sampler-steps", type=int, default=50)
     ap.add_argument("--chars", type=int, default=9)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what is reported beside `value` "
+                    "(roofline pass, other launch modes, UNet step latency, reference default, configs #5 / #4, CPU baseline); "
+                    "off: the run does only what `value` needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-config1", action="store_true", help="the CPU baseline also runs BASELINE config #1 in full (256x256, 10 steps: "
-                    "minutes of host time; off by default so that the bench command stays a few minutes long)")
-    ap.add_argument("--no-mode-table", action="store_true", help="skip the extra passes in the other launch modes")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the short BASELINE config #5 (--fp8) and config #4 (768x768, "
-                    "batch 8, 12 characters) passes that the default single-GPU config-#2 run appends under `config5` / `config4`")
+                    "minutes of host time; off by default so that the --full command stays a few minutes long)")
+    ap.add_argument("--no-mode-table", action="store_true", help="--full without the extra passes in the other launch modes")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full without the short BASELINE config #5 (--fp8) and config #4 "
+                    "(768x768, batch 8, 12 characters) passes that a single-GPU config-#2 run appends under `config5` / `config4`")
     ap.add_argument("--in-flight", type=int, default=3, help="batches sampled concurrently per GPU, one launch stream each "
                     "(same-box on MI355X: 1 -> 5.7, 2 -> 7.13, 3 -> 7.67, 4 -> 6.0 images/s)")
     ap.add_argument("--fp8", action="store_true", help="BASELINE config #5 arithmetic: every linear of the 640- / 1280-channel "
@@ -77,7 +85,7 @@ def parse():
                     "self-attention's Q K^T / P V on e4m3 operands (UDT_FP8_ATTN=0: bf16 attention)")
     ap.add_argument("--noise-iters", type=int, default=10, help="noise search iterations of the reference-default measurement "
                     "(configs/test.yaml:14 noise_iters: 10, batch_size 1): reported as images_per_s_reference_default")
-    ap.add_argument("--no-reference-default", action="store_true", help="skip the reference-default (B = 1, noise search) pass")
+    ap.add_argument("--no-reference-default", action="store_true", help="--full without the reference-default (B = 1, noise search) pass")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when bench.py launches its own ranks")
     ap.add_argument("--stub", action="store_true", help="host-logic self-test on the CPU (gloo, a stub engine): rank spawning, "
                     "image sharding, the single all-gather per global batch and the JSON line; the numbers mean nothing")
@@ -143,6 +151,38 @@ def dump_outputs(out_dir: str, outputs: dict) -> None:
         np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
 
 
+def fill_weights_(module: torch.nn.Module, device: torch.device, threads: int = 16) -> None:
+    """synth.fill_module_(module), each parameter then moved to `device`, by `threads` workers: the synthetic weights are a
+    pure function of each parameter's name and shape, so neither the order nor the thread changes a value.  For the 1.36 G
+    parameters of the engine this takes ~1 s on MI355X, against ~5 s to draw them on one thread and ~8 s for one model.to()
+    of the 5.4 GB from pageable host memory."""
+    from concurrent.futures import ThreadPoolExecutor
+    from udifftext_amd import synth
+
+    def fill(item):
+        name, p = item
+        if synth.is_computed_buffer(name):
+            return
+        with torch.no_grad():                    # (grad mode is per thread)
+            p.data = synth.synthetic_tensor(name, tuple(p.shape)).to(device, p.dtype)
+
+    with ThreadPoolExecutor(max(1, min(threads, os.cpu_count() or 1))) as ex:
+        list(ex.map(fill, module.named_parameters()))
+
+
+def build_engine(device: torch.device):
+    """pipeline.build_engine(device) with the weights filled by fill_weights_: the same engine, the same values"""
+    from sgm.util import instantiate_from_config, skip_param_init
+    from udifftext_amd import config as C
+    with skip_param_init():
+        model = instantiate_from_config(C.default_model_config().model)
+    fill_weights_(model, device)
+    model.to(device)                             # the buffers
+    model.eval()
+    model.freeze()
+    return model
+
+
 def physical_cores() -> int:
     try:
         import psutil
@@ -179,8 +219,8 @@ def extra_config(flags: list, steps: int, warmup: int, value_bf16: float | None 
     code path as a direct `python bench.py <flags>` run: own engine, own hipGraphs, same barriers around exactly `steps` timed steps),
     reduced to the keys that identify the workload and its numbers.  Reported beside `value`, never as it."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline",
-           "--no-reference-default", "--no-mode-table", "--no-extra-configs"] + flags
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--full",
+           "--no-cpu-baseline", "--no-reference-default", "--no-mode-table", "--no-extra-configs"] + flags
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "UDT_BENCH_FORCE_DIST")}
     t0 = time.perf_counter()
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT)
@@ -290,6 +330,49 @@ def stub_main(args, world: int, rank: int) -> None:
         dist.destroy_process_group()
 
 
+def baseline_config_id(args, world: int, G: int) -> str:
+    """the BASELINE.json configuration these arguments run ("non-baseline shape" if none)"""
+    return ("BASELINE.json configs[1]" if (args.size, args.batch, args.chars, args.sampler_steps, G, args.fp8) == (512, 4, 9, 50, 4 * world, False)
+            else "BASELINE.json configs[4]" if (args.fp8 and (args.size, args.sampler_steps, G, world) == (512, 50, 32, 8))
+            else ("BASELINE.json configs[4] arithmetic (fp8 MFMA attention / linear path), per-GPU share: batches of 4 of the 32 images "
+                  "that config shards over 8 GPUs, on %d GPU(s)" % world) if (args.fp8 and (args.size, args.batch, args.sampler_steps) == (512, 4, 50))
+            else "BASELINE.json configs[2]" if (args.size, args.sampler_steps, G, world) == (512, 50, 64, 8)
+            else "BASELINE.json configs[3]" if (args.size, args.batch, args.chars, args.sampler_steps) == (768, 8, 12, 50)
+            else "non-baseline shape")
+
+
+def headline(args, world: int, G: int, elapsed: float, graphs_on: bool) -> dict:
+    """the line of a plain run: `value` over the K timed steps and the workload it was measured on (--full adds the rest)"""
+    value = args.steps * G / elapsed
+    per_rank = G // world
+    return {
+        "metric": f"{args.size}x{args.size} {args.sampler_steps}-step denoised images/sec (UDiffText hot path: conditioner + "
+                  f"{args.sampler_steps} CFG Euler steps + VAE decode)",
+        "value": value, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak" if args.global_batch <= 0 else "strong",
+        "vs_baseline": None, "data": "synthetic",
+        "dtype": "fp8" if args.fp8 else "bf16",
+        "dtype_note": ("MX8 MFMA (v_mfma_scale_f32_32x32x64_f8f6f4: e4m3 elements, one E8M0 scale per 32 K-elements of an activation "
+                       "row written by the PRODUCING kernel's epilogue, per-output-channel weight scales) for every linear of the "
+                       "640- / 1280-channel transformer blocks (q|k|v, to_out, GEGLU, ff.net[2], proj_out: 69 % of the linear "
+                       "FLOPs; the 320-channel level's K = 320 projections are epilogue-bound and stay bf16, as do the "
+                       "convolutions) and for the self-attention's Q K^T and P V at all three levels (q, k block-scaled along the "
+                       "head dimension, v fixed-scale, probabilities as e4m3; text cross-attention bf16); fp32 accumulation, "
+                       "statistics, softmax maxima / normalisation and sampler state") if args.fp8 else
+                      "bf16 storage + MFMA, fp32 accumulation / statistics / softmax / sampler state",
+        "config": {"workload": f"{args.size}x{args.size}, {args.sampler_steps} Euler/DDIM(eta 0) steps, CFG 5.0, {args.chars}-char "
+                               f"labels, noise_iters 0; global batch {G} per step sharded over {world} GPU(s) = {per_rank} "
+                               f"images per GPU in micro-batches of {args.batch}: every UNet call runs ONE batch of "
+                               f"{args.batch} ({2 * args.batch * max(args.fuse, 1)} samples with CFG); {args.in_flight} such "
+                               f"batch(es) in flight per GPU on separate launch streams; " + baseline_config_id(args, world, G),
+                   "global_batch": G, "parallelism": f"dp{world} (images sharded contiguously, per-image seeds, one "
+                                                     "all-gather of frames per global batch)",
+                   "weights": "synthetic (name-keyed recipe), 1361.2 M parameters",
+                   "launch": "hipGraph replay of the sampler steps" if graphs_on else "eager kernel launches",
+                   "in_flight": args.in_flight, "batches_per_unet_call": max(args.fuse, 1) if args.fuse else "auto"},
+    }
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -324,11 +407,10 @@ def main():
     Hnn_fp8_attention = Hnn.fp8_attention
     torch.set_grad_enabled(False)
     with contextlib.redirect_stdout(sys.stderr):          # the conditioner announces its embedders like the reference does;
-        model = pipeline.build_engine(dev)                # stdout carries the ONE JSON line only
+        model = build_engine(dev)                         # stdout carries the ONE JSON line only
     sampler = pipeline.init_sampling(args.sampler_steps, 5.0, dev)
     cfgs = C.default_runtime_config(steps=args.sampler_steps, batch_size=args.batch, noise_iters=0, gpu=local_rank)
     G = args.global_batch if args.global_batch > 0 else args.batch * world
-    weak = args.global_batch <= 0
 
     def make_global_batch(i):
         # identical on every rank (same seed): each rank slices its shard out of it
@@ -372,12 +454,19 @@ def main():
     assert frames.shape[0] == G and bool(torch.isfinite(frames).all())
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, {"frames": frames})
+    graphs_on = bool(getattr(sampler, "use_graphs", False))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, G, elapsed, graphs_on)), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- roofline pass: graph replay issues no per-launch host calls, so the per-kernel HIP events (udt_prof_*,
     # recorded on the launch stream around every launch of the three MFMA classes) are taken on ONE extra pass of one
     # local batch with eager launches on a single stream, right after the timed region
     import sgm.modules.diffusionmodules.sampling as S
-    graphs_on = bool(getattr(sampler, "use_graphs", False))
     sampler.use_graphs = False
     dual_prev, S.DUAL_STREAM = S.DUAL_STREAM, False     # one launch stream: every kernel is timed alone on the chip
     lo, hi = parallel.shard_range(G, rank, world)
@@ -524,29 +613,8 @@ def main():
                                     "hipGraphs with batches in flight, where launches of two streams overlap)",
                      "whole_path_frac_of_peak": value * fpi / (world * PEAK_BF16),
                      "whole_path_frac_of_fp8_peak": (value * fpi / (world * 2 * PEAK_BF16)) if args.fp8 else None})
-        cfg_id = ("BASELINE.json configs[1]" if (args.size, args.batch, args.chars, args.sampler_steps, G, args.fp8) == (512, 4, 9, 50, 4 * world, False)
-                  else "BASELINE.json configs[4]" if (args.fp8 and (args.size, args.sampler_steps, G, world) == (512, 50, 32, 8))
-                  else ("BASELINE.json configs[4] arithmetic (fp8 MFMA attention / linear path), per-GPU share: batches of 4 of the 32 images "
-                        "that config shards over 8 GPUs, on %d GPU(s)" % world) if (args.fp8 and (args.size, args.batch, args.sampler_steps) == (512, 4, 50))
-                  else "BASELINE.json configs[2]" if (args.size, args.sampler_steps, G, world) == (512, 50, 64, 8)
-                  else "BASELINE.json configs[3]" if (args.size, args.batch, args.chars, args.sampler_steps) == (768, 8, 12, 50)
-                  else "non-baseline shape")
-        per_rank = G // world
-        line = {
-            "metric": f"{args.size}x{args.size} {args.sampler_steps}-step denoised images/sec (UDiffText hot path: conditioner + "
-                      f"{args.sampler_steps} CFG Euler steps + VAE decode)",
-            "value": value, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak" if weak else "strong",
-            "vs_baseline": None, "data": "synthetic",
-            "dtype": "fp8" if args.fp8 else "bf16",
-            "dtype_note": ("MX8 MFMA (v_mfma_scale_f32_32x32x64_f8f6f4: e4m3 elements, one E8M0 scale per 32 K-elements of an activation "
-                           "row written by the PRODUCING kernel's epilogue, per-output-channel weight scales) for every linear of the "
-                           "640- / 1280-channel transformer blocks (q|k|v, to_out, GEGLU, ff.net[2], proj_out: 69 % of the linear "
-                           "FLOPs; the 320-channel level's K = 320 projections are epilogue-bound and stay bf16, as do the "
-                           "convolutions) and for the self-attention's Q K^T and P V at all three levels (q, k block-scaled along the "
-                           "head dimension, v fixed-scale, probabilities as e4m3; text cross-attention bf16); fp32 accumulation, "
-                           "statistics, softmax maxima / normalisation and sampler state") if args.fp8 else
-                          "bf16 storage + MFMA, fp32 accumulation / statistics / softmax / sampler state",
+        line = headline(args, world, G, elapsed, graphs_on)
+        line.update({
             "value_one_batch": (value if (args.in_flight == 1 and args.fuse == 1) else other_modes.get("one_batch_at_a_time")),
             "value_one_batch_note": "the same K steps with ONE batch of --batch images on the GPU at a time (no batches in "
                                     "flight): the number that does not depend on how launch streams share the chip",
@@ -555,16 +623,6 @@ def main():
             "unet_ms_per_sampler_step": unet_ms,
             "unet_ms_note": f"one batch of {args.batch} alone on the whole GPU (latency of one UNet call on its CFG pair, one launch "
                             "stream, + the fused CFG/Euler update); with batches in flight the per-batch cost is lower",
-            "config": {"workload": f"{args.size}x{args.size}, {args.sampler_steps} Euler/DDIM(eta 0) steps, CFG 5.0, {args.chars}-char "
-                                   f"labels, noise_iters 0; global batch {G} per step sharded over {world} GPU(s) = {per_rank} "
-                                   f"images per GPU in micro-batches of {args.batch}: every UNet call runs ONE batch of "
-                                   f"{args.batch} ({2 * args.batch * max(args.fuse, 1)} samples with CFG); {args.in_flight} such "
-                                   f"batch(es) in flight per GPU on separate launch streams; " + cfg_id,
-                       "global_batch": G, "parallelism": f"dp{world} (images sharded contiguously, per-image seeds, one "
-                                                         "all-gather of frames per global batch)",
-                       "weights": "synthetic (name-keyed recipe), 1361.2 M parameters",
-                       "launch": "hipGraph replay of the sampler steps" if graphs_on else "eager kernel launches",
-                       "in_flight": args.in_flight, "batches_per_unet_call": max(args.fuse, 1) if args.fuse else "auto"},
             "roofline": conv,
             "roofline_classes": {
                 "gemm": cls("linears + 1x1 convolutions: lg::lgemm_kernel (lean co-resident family; plain / GEGLU / LayerNorm-folded) "
@@ -573,8 +631,8 @@ def main():
                 "attention": cls("flash attention: " + ("attn_d64_mx8_kernel (UNet self-attention on e4m3 operands, head_dim 64; priced against the bf16 peak like the class)"
                                                  if args.fp8 and Hnn_fp8_attention() else "attn_d64_v2_kernel (UNet self-attention, head_dim 64)")
                                  + " + attn_d512_q64_kernel (VAE mid block, one head of 512)", attn_flops, attn_bytes, attn_ms, attn_launches)},
-        }
-        if world == 1 and not args.no_extra_configs and cfg_id == "BASELINE.json configs[1]":
+        })
+        if world == 1 and not args.no_extra_configs and baseline_config_id(args, world, G) == "BASELINE.json configs[1]":
             # the other single-GPU configurations of BASELINE.json on the same box, back to back with the line above (the GPU is idle
             # here: this process only holds memory); `value` stays config #2
             line["config5"] = extra_config(["--fp8"], args.steps, args.warmup, value)

@@ -89,3 +89,30 @@ def test_bench_dump_outputs_samples_an_output_over_the_budget(tmp_path, monkeypa
     assert v.dtype == np.float32 and i.dtype == np.float64 and v.shape == i.shape == (100,)
     assert np.array_equal(v, t.numpy().reshape(-1)[i.astype(np.int64)])
     assert np.array_equal(v, np.load(tmp_path / "b" / "frames_sample.npy"))
+
+
+def test_bench_threaded_weight_fill_equals_fill_module():
+    """bench.py builds its engine with the synthetic weights drawn on several threads and moved to the device one tensor at a
+    time (fill_weights_): every value is synth.fill_module_'s, bit for bit (a reduced-width UNet, on the host)"""
+    import importlib.util
+    import torch
+    import udifftext_amd  # noqa: F401  (puts the sgm mirror on sys.path)
+    from sgm.modules.diffusionmodules.openaimodel import UnifiedUNetModel
+    from sgm.util import skip_param_init
+    from udifftext_amd import synth
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    def unet():
+        with skip_param_init():
+            return UnifiedUNetModel(in_channels=9, ctrl_channels=0, model_channels=64, out_channels=4, num_res_blocks=1,
+                                    attention_resolutions=[1, 2], channel_mult=[1, 2], num_head_channels=64,
+                                    use_linear_in_transformer=True, transformer_depth=1, t_context_dim=128,
+                                    save_attn_type=["t_attn"])
+    want, got = unet(), unet()
+    synth.fill_module_(want)
+    bench.fill_weights_(got, torch.device("cpu"), threads=4)
+    sw, sg = want.state_dict(), got.state_dict()
+    assert list(sw) == list(sg) and len(sw) > 100
+    assert all(sw[k].dtype == sg[k].dtype and torch.equal(sw[k], sg[k]) for k in sw)
