@@ -152,8 +152,8 @@ def test_lms_vs_reference_golden(engine, cond256, cuda):
 
 
 def test_graph_replay_matches_eager_launches(engine, cond256, cond256b, cuda):
-    """6 steps (the 4-slot derivative ring wraps), captured per (step index, plan) and replayed — bit-equal to eager launches;
-    then a second batch through rebind(), and a run from init_step 2 (empty history) on the same runner"""
+    """6 steps (the 4-slot derivative ring wraps), captured per step index and replayed — bit-equal to eager launches;
+    then a second batch through rebind(), and a run from init_step 2 (empty history) on a runner of its own"""
     from udifftext_amd import pipeline
     (c, uc), (c2, uc2) = cond256, cond256b
     torch.manual_seed(5)

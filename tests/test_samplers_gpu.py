@@ -130,7 +130,7 @@ def test_sampler_vs_reference_golden(engine, cond256, sg, cuda, run):
 
 @pytest.mark.parametrize("name", NEW)
 def test_graph_replay_matches_eager_launches(engine, cond256, cuda, name):
-    """the same launches, captured per (step index, plan) and replayed — bit-equal; then a second batch through rebind()"""
+    """the same launches, captured per step index and replayed — bit-equal; then a second batch through rebind()"""
     from udifftext_amd import pipeline, synth
     batch, c, uc = cond256
     torch.manual_seed(5)

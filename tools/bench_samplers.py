@@ -51,7 +51,7 @@ def main():
         sampler = pipeline.init_sampling(n, 5.0, dev, sampler=kind)
         cfgs = C.default_runtime_config(steps=n, batch_size=args.batch, noise_iters=0)
         sig = [float(s) for s in sampler.discretization(n, device="cpu")]
-        evals = n if kind == "euler" else sum(len(p) for _, p in sampler.plans(sig))
+        evals = sum(len(p) for _, p in sampler.plans(sig))
 
         def run(idx):
             return parallel.predict_sharded(cfgs, model, sampler, [batches[i] for i in idx], [seeds[i] for i in idx],

@@ -12,10 +12,12 @@ concat channels of the UNet input).  Attention maps are only emitted where they 
 The heavier side paths (attend-and-excite: needs autograd through the UNet; attention-map plots / GIFs) are
 out of scope and raise.
 
-HeunEDMSampler, EulerAncestralSampler, DPMPP2SAncestralSampler and DPMPP2MSampler (reference :140-215, :423-567) run the
-same UNet call followed by ONE udt_cfg_sampler_step launch per evaluation; each supplies a per-step plan of host
-coefficients (``Eval``, bottom of this file).  LinearMultistepSampler (reference :180-215) ends every evaluation in
-ONE udt_cfg_multistep_step launch instead (``MultistepEval``: to_d and the sum over a ring of derivative buffers).
+Every sampler describes step i as a plan of UNet evaluations, each ending in ONE fused launch: ``EulerEval``
+(udt_cfg_euler_step, the step above: EulerEDMSampler), ``Eval`` (udt_cfg_sampler_step: HeunEDMSampler, EulerAncestralSampler,
+DPMPP2SAncestralSampler, DPMPP2MSampler, reference :140-215, :423-567) or ``MultistepEval`` (udt_cfg_multistep_step:
+LinearMultistepSampler, reference :180-215; to_d and the sum over a ring of derivative buffers).  One loop (``_PlanSampler``)
+runs the plans of any of them as eager launches or hipGraph replays (``_GraphedSteps``): alone, on a lane of
+pipeline.predict_many, or as several batches in flight.
 """
 from __future__ import annotations
 
@@ -117,6 +119,67 @@ def _is_capture_failure(e: BaseException) -> bool:
     return "captur" in msg or "graph" in msg
 
 
+# ================================================================================================================== plans
+# A sampler supplies per step i its ``plan``: the UNet evaluations of the step with their sigma and float64 host coefficients,
+# over named fp32 NCHW buffers — "x" (the latent) and the scratch / history buffers the plans name ("t": Euler predictor /
+# midpoint, "h0" / "h1": denoised history, "d0" ...: derivative ring).  Each evaluation is the CFG pair's UNet call on its source
+# buffer followed by ONE fused launch.  The same plan runs as eager launches, inside one hipGraph per step index, or (tests) as
+# plain torch arithmetic.
+
+
+class EulerEval(NamedTuple):
+    """one UNet evaluation + the in-place Euler update of src from sigma to sigma_next (udt_cfg_euler_step: _Stepper.step)"""
+    sigma: float
+    sigma_next: float
+    src: str = "x"
+
+
+class Eval(NamedTuple):
+    """one UNet evaluation + its fused update (udt_cfg_sampler_step), with den = CFG(src + c_out*eps_u, src + c_out*eps_c),
+    c_out = -quantised sigma: out = kx*src + kd*den(src, sigma) + ka*aux + kp*prev + kn*noise[step]"""
+    sigma: float                       # UNQUANTISED sigma of the call (c_in, c_out and the timestep use its quantised value)
+    src: str
+    out: str
+    kx: float = 0.0
+    kd: float = 0.0
+    aux: Optional[str] = None
+    ka: float = 0.0
+    prev: Optional[str] = None
+    kp: float = 0.0
+    kn: float = 0.0
+    den_out: Optional[str] = None
+
+
+class MultistepEval(NamedTuple):
+    """one UNet evaluation + the fused linear-multistep update (udt_cfg_multistep_step): d = (src - den(src, sigma))/sigma;
+    out = src + (k0*d + k_1*hist_1 + ...) over ``hist`` = ((buffer, k), ...), the older derivatives newest first; d_out <- d"""
+    sigma: float                       # UNQUANTISED sigma (to_d); c_in, c_out and the timestep use its quantised value
+    src: str
+    out: str
+    d_out: str
+    k0: float
+    hist: tuple = ()
+
+
+def plan_buffers(plans) -> list:
+    """the names of the buffers ``plans`` ((step, plan) pairs) read or write, besides the latent "x", in first-use order"""
+    names = []
+    for _, plan in plans:
+        for e in plan:
+            if isinstance(e, EulerEval):
+                used = (e.src,)
+            elif isinstance(e, MultistepEval):
+                used = (e.src, e.out, e.d_out) + tuple(b for b, _ in e.hist)
+            else:
+                used = (e.src, e.out, e.aux, e.prev, e.den_out)
+            names.extend(b for b in used if b and b != "x" and b not in names)
+    return names
+
+
+def plans_add_noise(plans) -> bool:
+    """does an evaluation of ``plans`` add the step's ancestral draw?"""
+    return any(isinstance(e, Eval) and e.kn != 0.0 for _, plan in plans for e in plan)
+
 class _Stepper:
     """Step-invariant device state of one sampling run + the fused per-step launch sequence."""
 
@@ -195,11 +258,14 @@ class _Stepper:
         ops.cfg_euler_step(x, eps, sigma, sigma_next, self.scale, denoised=denoised, c_out=-sq)
 
     def run_plan(self, bufs: Dict[str, torch.Tensor], plan, noise: Optional[torch.Tensor] = None) -> None:
-        """one step of a non-Euler sampler: per evaluation of ``plan`` (a tuple of ``Eval`` / ``MultistepEval``), the UNet call on
-        its source buffer and one udt_cfg_sampler_step / udt_cfg_multistep_step launch; ``bufs`` maps the plan's buffer names to
-        fp32 NCHW tensors, ``noise`` is this step's ancestral draw"""
+        """one sampler step: per evaluation of ``plan`` (a tuple of ``EulerEval`` / ``Eval`` / ``MultistepEval``), the UNet call
+        on its source buffer and its fused launch; ``bufs`` maps the plan's buffer names to fp32 NCHW tensors, ``noise`` is this
+        step's ancestral draw"""
         for e in plan:
             src = bufs[e.src]
+            if isinstance(e, EulerEval):
+                self.step(src, e.sigma, e.sigma_next)
+                continue
             eps, sq = self.unet_eps(src, e.sigma)
             if isinstance(e, MultistepEval):
                 ops.cfg_multistep_step(src, eps, -sq, self.scale, e.sigma, (e.k0,) + tuple(k for _, k in e.hist),
@@ -241,22 +307,33 @@ class _GraphedSteps:
     replayed for every later batch of the same shape: the host then issues 50 graph launches per batch instead of
     ~29,000 kernel launches (8 ms of Python / ctypes time per step), and the command processor walks the kernels
     back to back.  Conditioning (text k|v projections, concat channels) lives in static device buffers that
-    ``rebind`` refreshes in place; the latent is a static fp32 buffer."""
+    ``rebind`` refreshes in place; the latent ``x``, the scratch / history buffers the plans name and, if a plan adds
+    noise, the run's ancestral draws ([steps, B, 4, h, w], refreshed per run by ``load``) are static fp32 buffers.
+    A runner serves one sequence of ``plans`` ((step, plan) pairs; by default Euler over every step of ``sig``), one
+    graph per step index."""
 
-    def __init__(self, model, cond, uc, batch_size, latent_hw, scale, sig, cu_share: int = 1):
+    def __init__(self, model, cond, uc, batch_size, latent_hw, scale, sig, cu_share: int = 1, plans=None):
         # cu_share > 1: this runner is one of several batches in flight; its launches are planned for 1/cu_share of
         # the CUs and its UNet stays on one stream (the concurrency comes from the other batches)
         self.cu_share = int(cu_share)
         self.st = _Stepper(model, cond, uc, batch_size, latent_hw, scale, two_streams=None if cu_share == 1 else False)
         self.st.cu_share = self.cu_share
         self.fingerprint = weights_fingerprint(model)
+        if plans is None:
+            plans = [(i, (EulerEval(sig[i], sig[i + 1]),)) for i in range(len(sig) - 1)]
+        self.plans = dict(plans)
         h, w = latent_hw
         self.x = torch.zeros((batch_size, 4, h, w), dtype=torch.float32, device=self.st.dev)
-        self.sig = list(sig)
+        self.bufs = {"x": self.x}
+        for name in plan_buffers(plans):                  # e.g. LinearMultistepSampler's derivative ring d0 .. d{order-1}
+            self.bufs[name] = torch.zeros_like(self.x)
+        self.noise = (torch.zeros((len(plans),) + tuple(self.x.shape), dtype=torch.float32, device=self.st.dev)
+                      if plans_add_noise(plans) else None)
         self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self.pool = torch.cuda.graph_pool_handle()
         self.capture_stream = torch.cuda.Stream(device=self.st.dev)
         self.warm = False
+        self.last_replay: Optional[torch.cuda.Event] = None
 
     def rebind(self, cond, uc) -> bool:
         """refresh the static conditioning buffers for a new batch; False if the launch sequence would differ"""
@@ -273,48 +350,72 @@ class _GraphedSteps:
         ops.nhwc_set_channels(concat, st.xin, 4)
         return True
 
+    def load(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None) -> None:
+        """the run's latent and, if a plan adds noise, its ancestral draws (draw_step_noise)"""
+        self.x.copy_(x)
+        if self.noise is not None and noise is not None:
+            self.noise.copy_(noise)
+
     def _capture(self, i: int) -> torch.cuda.CUDAGraph:
-        st = self.st
-        st.emb_rows(st.quantise(self.sig[i])[0])                 # time-embedding rows are cached outside the graph
+        st, plan = self.st, self.plans[i]
+        noise = self.noise[list(self.plans).index(i)] if self.noise is not None else None
+        for e in plan:
+            st.emb_rows(st.quantise(e.sigma)[0])             # time-embedding rows are cached outside the graph
         if not self.warm:
             # one eager pass on the capture stream: sets kernel attributes, allocates the library's pages
             torch.cuda.synchronize()
             with torch.cuda.stream(self.capture_stream):
-                keep = self.x.clone()
-                st.step(self.x, self.sig[i], self.sig[i + 1])
-                self.x.copy_(keep)
+                keep = {k: v.clone() for k, v in self.bufs.items()}
+                st.run_plan(self.bufs, plan, noise)
+                for k, v in keep.items():
+                    self.bufs[k].copy_(v)
             torch.cuda.synchronize()
             self.warm = True
         g = torch.cuda.CUDAGraph()
         # thread_local: other threads of the process (the RCCL watchdog under torch.distributed) may touch the
         # HIP runtime while this thread captures
         with torch.cuda.graph(g, pool=self.pool, stream=self.capture_stream, capture_error_mode="thread_local"):
-            st.step(self.x, self.sig[i], self.sig[i + 1])
+            st.run_plan(self.bufs, plan, noise)
         self.graphs[i] = g
         return g
 
-    def run(self, x: torch.Tensor, steps) -> torch.Tensor:
-        self.x.copy_(x)
-        for i in steps:
-            g = self.graphs.get(i)
-            if g is None:
-                g = self._capture(i)
-            g.replay()
-        out = self.x.clone()
-        self.st.check()                       # one sync per sampling loop: surfaces a stream-K time-out as UdtError
-        return out
+    def capture(self) -> None:
+        """capture every step not captured yet, on the runner's own stream, ordered behind the current stream"""
+        missing = [i for i in self.plans if i not in self.graphs]
+        if missing:
+            lane = torch.cuda.current_stream()
+            self.capture_stream.wait_stream(lane)
+            for i in missing:
+                self._capture(i)
+            lane.wait_stream(self.capture_stream)
 
 
-AAE_GRAPH = os.environ.get("UDT_AAE_GRAPH", "1") != "0"      # hipGraph replay of the attend-and-excite gradient (A/B switch)
+class _RunnerKey(NamedTuple):
+    """what a cached graph runner was built for: engine, latent shape, guidance scale, device, the exact plan sequence (schedule
+    and init_step) and, on the lanes, its slot of n_lanes"""
+    model: int
+    shape: tuple
+    scale: float
+    device: Optional[int]
+    plans: tuple
+    slot: int = 0
+    n_lanes: int = 1
 
 
-class EulerEDMSampler(EDMSampler):
+class _PlanSampler:
+    """the sampling loop of every sampler here: a sampler supplies ``step_plan``; this runs the plans as eager launches or
+    hipGraph replays — alone (``_sample``), on the lanes of pipeline.predict_many (``sample_lane``) or as several batches in
+    flight (``sample_in_flight``) — and draws the initial noise (the noise search does not depend on the sampler)"""
     use_graphs = os.environ.get("UDT_GRAPHS", "1") != "0"      # hipGraph replay of the main loop (eager launches if off)
+    uses_noise = False                 # ancestral samplers: one rng draw [B,4,h,w] per step, the last step included
 
-    def possible_correction_step(self, euler_step, x, d, dt, next_sigma, denoiser, cond, uc):
-        return euler_step
+    def step_plan(self, sig, i: int, init_step: int = 0) -> tuple:
+        """the evaluations of step i (sig: host sigmas, len num_steps + 1) -> tuple of EulerEval / Eval / MultistepEval"""
+        raise NotImplementedError
 
-    # ----------------------------------------------------------------------------------------- helpers
+    def plans(self, sig, init_step: int = 0):
+        return [(i, self.step_plan(sig, i, init_step)) for i in self.get_sigma_gen(len(sig), init_step=init_step)]
+
     def _host_sigmas(self, num_steps=None):
         n = self.num_steps if num_steps is None else num_steps
         return [float(s) for s in self.discretization(n, device="cpu")]
@@ -322,8 +423,18 @@ class EulerEDMSampler(EDMSampler):
     def _check_fast_path(self):
         if not isinstance(self.guider, VanillaCFG):
             raise NotImplementedError("the fused MI355X step implements VanillaCFG guidance")
-        if self.s_churn != 0.0:
-            raise NotImplementedError("s_churn > 0 (stochastic sampling) is not used by UDiffText (util.py:39)")
+        if getattr(self, "s_churn", 0.0) != 0.0:
+            raise NotImplementedError("s_churn > 0 (stochastic sampling) is not implemented by the fused samplers "
+                                      "(UDiffText uses 0, util.py:39)")
+
+    def draw_step_noise(self, shape, device, num_steps=None, init_step: int = 0) -> Optional[torch.Tensor]:
+        """the ancestral draws of one run: one rng.randn of ``shape`` per step from init_step on, in step order, as ONE device
+        buffer [steps, *shape] (None for the deterministic samplers).  Drawn up front so that graph replays can read a slice
+        per step; the values equal per-step draws because the CPU streams are sequential."""
+        if not self.uses_noise:
+            return None
+        n = len(self._host_sigmas(num_steps)) - 1 - init_step
+        return rng.randn_steps_on(n, shape, device)
 
     # -------------------------------------------------------------------------------------- noise search
     def get_init_noise(self, cfgs, model, cond, batch, uc=None):
@@ -372,6 +483,201 @@ class EulerEDMSampler(EDMSampler):
         print(f"Init local loss: Best {score.min().item()} Worst {score.max().item()}")
         stack = torch.stack(cands, 0)                                     # [iters, B, 4, h, w]
         return stack[best, torch.arange(shape[0], device=dev)].contiguous()
+
+    # --------------------------------------------------------------------------------------------- loop
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, init_step=0, batch=None, aae_enabled=False, detailed=False,
+                 name=None, noise: Optional[torch.Tensor] = None, **kwargs):
+        """reference __call__(denoiser, x, cond, uc, num_steps) [+ init_step]; ``noise``: the run's ancestral draws
+        (draw_step_noise), drawn here when not given"""
+        if aae_enabled:
+            raise NotImplementedError(f"attend-and-excite is implemented for EulerEDMSampler only, not {type(self).__name__}")
+        if detailed:
+            raise NotImplementedError(f"detailed attention-map dumps are implemented for EulerEDMSampler only, not {type(self).__name__}")
+        return self._sample(denoiser, x, cond, uc, num_steps, init_step, noise)
+
+    def _sample(self, model, x, cond, uc=None, num_steps=None, init_step=0, noise: Optional[torch.Tensor] = None):
+        """the plain sampling loop: hipGraph replay, eager launches if graphs are off or unavailable"""
+        self._check_fast_path()
+        require_gpu(x, type(self).__name__)
+        uc = default(uc, cond)
+        sig = self._host_sigmas(num_steps)
+        x = x.float().contiguous()
+        if noise is None:
+            noise = self.draw_step_noise(x.shape, x.device, num_steps, init_step)
+        x *= (1.0 + sig[0] ** 2.0) ** 0.5                                  # in place, like the reference :54
+        plans = self.plans(sig, init_step)
+        if self.use_graphs:
+            out = self._run_graphed(model, x, cond, uc, sig, plans, noise)
+            if out is not None:
+                return out
+        stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale)
+        bufs = {"x": x}
+        for name in plan_buffers(plans):
+            bufs[name] = torch.empty_like(x)
+        for i, plan in plans:
+            stepper.run_plan(bufs, plan, noise[i - init_step] if noise is not None else None)
+        stepper.check()
+        return x
+
+    def _runner_key(self, model, x, plans, slot: int = 0, n_lanes: int = 1) -> _RunnerKey:
+        return _RunnerKey(id(model), tuple(x.shape), float(self.guider.scale), x.device.index, tuple(plans), slot, n_lanes)
+
+    def _run_graphed(self, model, x, cond, uc, sig, plans, noise):
+        """replay (capturing on first use) the hipGraphs of this sampling configuration; None -> eager launches"""
+        key = self._runner_key(model, x, plans)
+        cache = self.__dict__.setdefault("_graphed", {})
+        try:
+            gs = cache.get(key)
+            if gs is not None and gs.fingerprint != weights_fingerprint(model):
+                gs = None                                       # weights changed under the captured graphs
+            if gs is None or not gs.rebind(cond, uc):
+                cache.clear()                                   # one configuration at a time (each holds a memory pool)
+                gs = _GraphedSteps(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale, sig, plans=plans)
+                cache[key] = gs
+            gs.load(x, noise)
+            gs.capture()
+            for i in gs.plans:
+                gs.graphs[i].replay()
+            out = gs.x.clone()
+            gs.st.check()                       # one sync per sampling loop: surfaces a stream-K time-out as UdtError
+            return out
+        except RuntimeError as e:
+            if not _is_capture_failure(e):                      # kernel status errors, OOM, ...: never hidden
+                raise
+            if not self.__dict__.get("_graph_warned"):
+                print(f"[udifftext_amd] hipGraph capture unavailable ({e}); using eager launches", file=sys.stderr)
+                self._graph_warned = True
+            self.use_graphs = False
+            cache.clear()
+            return None
+
+    # ------------------------------------------------------------------------------- batches in flight
+    def _lane_runner(self, model, x, cond, uc, slot, n_lanes, sig, plans):
+        """this lane's graph runner, rebound to the batch, with every graph of ``plans`` captured.
+        A runner that leaves the cache may still have graph replays queued on a lane stream (nothing here synchronises the
+        host): it is parked in ``_retired`` — its graphs and private memory pool stay alive — until its ``last_replay`` event
+        has completed (checked here) or the caller has synchronised (pipeline.predict_many -> release_retired); runners of
+        the current call's lanes are never evicted."""
+        cache = self.__dict__.setdefault("_in_flight", {})
+        retired = self.__dict__.setdefault("_retired", [])
+        retired[:] = [r for r in retired if r.last_replay is not None and not r.last_replay.query()]
+        key = self._runner_key(model, x, plans, slot, n_lanes)
+        gs = cache.get(key)
+        if gs is not None and gs.fingerprint != weights_fingerprint(model):     # weights changed: the captured pointers are stale
+            retired.append(cache.pop(key))
+            gs = None
+        if gs is None or not gs.rebind(cond, uc):
+            gs = _GraphedSteps(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale, sig, cu_share=n_lanes, plans=plans)
+            if key in cache:
+                retired.append(cache.pop(key))
+            victims = [k for k in cache if (k.model, k.shape, k.n_lanes) != (key.model, key.shape, key.n_lanes)]
+            while len(cache) >= 8 and victims:                  # every runner owns a memory pool: keep the newest few
+                retired.append(cache.pop(victims.pop(0)))
+            cache[key] = gs
+        gs.capture()             # first use of this lane / shape (a capture synchronises the device once)
+        return gs
+
+    @staticmethod
+    def _finish(gs, stream, deferred_checks: Optional[list]) -> None:
+        """mark the runner's replays done once ``stream`` gets here; its error-word check now or into ``deferred_checks``"""
+        gs.last_replay = torch.cuda.Event()
+        gs.last_replay.record(stream)
+        if deferred_checks is None:
+            gs.st.check()
+        elif gs.st.check not in deferred_checks:
+            deferred_checks.append(gs.st.check)
+
+    def sample_lane(self, model, x, cond, uc, slot: int, n_lanes: int, init_step=0, deferred_checks: Optional[list] = None,
+                    noise: Optional[torch.Tensor] = None):
+        """the sampling loop of ONE batch on the CURRENT stream, as lane ``slot`` of ``n_lanes`` free-running lanes
+        (pipeline.predict_many): rebind this lane's runner to the batch, enqueue all graph replays, return the latent — no
+        host synchronisation and no event shared with the other lanes, so a lane runs condition -> sample -> decode back to
+        back while the launch thread is already feeding the next lane.  Launches are planned for 1 / n_lanes of the CUs
+        (cu_share), as in ``sample_in_flight``.  The runner's error-word check goes to ``deferred_checks``; ``noise``: the
+        batch's ancestral draws (drawn here when not given)."""
+        if n_lanes <= 1 or not self.use_graphs:
+            return self._sample(model, x, cond, uc, None, init_step, noise)
+        self._check_fast_path()
+        require_gpu(x, type(self).__name__)
+        uc = default(uc, cond)
+        sig = self._host_sigmas(None)
+        if noise is None:
+            noise = self.draw_step_noise(x.shape, x.device, None, init_step)
+        gs = self._lane_runner(model, x, cond, uc, slot, n_lanes, sig, self.plans(sig, init_step))
+        gs.load(x.float(), noise)
+        gs.x.mul_((1.0 + sig[0] ** 2.0) ** 0.5)
+        for i in gs.plans:
+            gs.graphs[i].replay()
+        out = gs.x.clone()
+        self._finish(gs, torch.cuda.current_stream(), deferred_checks)
+        return out
+
+    def sample_in_flight(self, model, xs, conds, ucs, init_step=0, deferred_checks: Optional[list] = None,
+                         streams: Optional[list] = None, noises: Optional[list] = None):
+        """run the sampling loops of SEVERAL independent batches concurrently (one launch stream + one set of
+        hipGraphs each, every stream planned for its share of the CUs) and return their latents.
+
+        One launch stream cannot keep the chip busy through every kernel's ramp-up, epilogue and tail; measured on
+        MI355X (512x512, batch 4): 14.0 ms per sampler step for one batch at a time, 10.9 ms per step and batch with
+        two batches in flight, 10.1 with three (pipeline.IN_FLIGHT).  Falls back to one batch after the other when
+        graphs are unavailable.
+
+        ``deferred_checks``: a list that receives the runners' error-word checks instead of running them here (each
+        check synchronises its stream) — a caller that keeps enqueuing work behind this call (pipeline.predict_many)
+        runs them once at its own synchronisation point.
+        ``streams``: launch streams to replay on, one per batch (default: the runners' capture streams).  A caller
+        that already owns one stream per batch passes them so that no further streams are active: hipStreams share a
+        small number of hardware queues (GPU_MAX_HW_QUEUES, 4 by default) and two busy streams on one queue serialise.
+        ``noises[k]``: batch k's ancestral draws (drawn here, in batch order, when not given)."""
+        n = len(xs)
+        if noises is None:
+            noises = [self.draw_step_noise(x.shape, x.device, None, init_step) for x in xs]
+        if n == 1 or not self.use_graphs:
+            return [self._sample(model, x, c, u, None, init_step, nz) for x, c, u, nz in zip(xs, conds, ucs, noises)]
+        self._check_fast_path()
+        sig = self._host_sigmas(None)
+        plans = self.plans(sig, init_step)
+        runners = []
+        for slot, (x, c, u, nz) in enumerate(zip(xs, conds, ucs, noises)):
+            require_gpu(x, type(self).__name__)
+            gs = self._lane_runner(model, x, c, default(u, c), slot, n, sig, plans)
+            gs.load(x.float(), nz)
+            gs.x.mul_((1.0 + sig[0] ** 2.0) ** 0.5)
+            runners.append(gs)
+        main = torch.cuda.current_stream()
+        lanes = list(streams[:n]) if streams is not None and len(streams) >= n else [gs.capture_stream for gs in runners]
+        for lane in lanes:
+            lane.wait_stream(main)
+        for i, _ in plans:                               # interleaved launches: every queue stays fed
+            for gs, lane in zip(runners, lanes):
+                with torch.cuda.stream(lane):
+                    gs.graphs[i].replay()
+        for lane in lanes:
+            main.wait_stream(lane)
+        outs = [gs.x.clone() for gs in runners]
+        for gs in runners:
+            self._finish(gs, main, deferred_checks)
+        return outs
+
+    def release_retired(self) -> None:
+        """drop the runners the lanes took out of their cache — call after the lanes' streams have been synchronised"""
+        self.__dict__.get("_retired", []).clear()
+
+    def invalidate_graphs(self) -> None:
+        """drop every captured hipGraph (explicit hook; the caches also notice changed weights by fingerprint)"""
+        self.__dict__.pop("_graphed", None)
+        self.__dict__.pop("_in_flight", None)
+
+
+AAE_GRAPH = os.environ.get("UDT_AAE_GRAPH", "1") != "0"      # hipGraph replay of the attend-and-excite gradient (A/B switch)
+
+
+class EulerEDMSampler(_PlanSampler, EDMSampler):
+    """reference sampling.py:218-420: one udt_cfg_euler_step evaluation per step (``EulerEval``) through the shared loop; the
+    attend-and-excite loop, the reference-shaped ``sampler_step`` and the ``detailed`` attention-map dump are its own"""
+
+    def possible_correction_step(self, euler_step, x, d, dt, next_sigma, denoiser, cond, uc):
+        return euler_step
 
     # --------------------------------------------------------------------------------- attend-and-excite
     def get_c_noise(self, x, model, sigma):
@@ -449,41 +755,34 @@ class EulerEDMSampler(EDMSampler):
         np.save(os.path.join(out_dir, f"seg_{save_name}.npy"), section)
         return section
 
-    # --------------------------------------------------------------------------------------------- loop
+    # ------------------------------------------------------------------------------------------- loop
+    def step_plan(self, sig, i, init_step=0):
+        return (EulerEval(sig[i], sig[i + 1]),)
+
     def __call__(self, model, x, cond, batch=None, uc=None, num_steps=None, init_step=0, name=None, aae_enabled=False,
                  detailed=False):
+        if not (aae_enabled or detailed):
+            return self._sample(model, x, cond, uc, num_steps, init_step)
         self._check_fast_path()
         require_gpu(x, "EulerEDMSampler")
         uc = default(uc, cond)
         if aae_enabled:
             return self._sample_with_attend_and_excite(model, x, cond, batch, uc, num_steps, init_step, name, detailed)
+        # reference sampling.py:384,344-346: at the middle step the text cross-attention maps of the configured layers are plotted
+        # and the label's per-character maps saved.  That one step runs with map emission (eager launches, the xattn chain); every
+        # other step is the fast step — the loop is the same Euler loop, so the latent equals the plain call's up to the two
+        # text-attention forms' rounding
         sig = self._host_sigmas(num_steps)
         x = x.float().contiguous()
         x *= (1.0 + sig[0] ** 2.0) ** 0.5                                  # in place, like the reference :54
-        if detailed:
-            # reference sampling.py:384,344-346: at the middle step the text cross-attention maps of the configured layers are
-            # plotted and the label's per-character maps saved.  That one step runs with map emission (eager launches, the xattn
-            # chain); every other step is the fast step — the loop is the same Euler loop, so the latent equals the plain call's
-            # up to the two text-attention forms' rounding
-            name = name if name is not None else (batch["name"][0] if batch is not None and "name" in batch else "sample")
-            stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale)
-            mid = (len(sig) - 1) // 2
-            for i in self.get_sigma_gen(len(sig), init_step=init_step):
-                stepper.step(x, sig[i], sig[i + 1], emit_maps=(i == mid))
-                if i == mid:
-                    attn_map = stepper.unet.save_attn_map(save_name=name, tokens=batch["label"][0])
-                    self.save_segment_map(attn_map, tokens=batch["label"][0], save_name=name)
-            stepper.check()
-            return x
-        if self.use_graphs:
-            out = self._run_graphed(model, x, cond, uc, sig, init_step)
-            if out is not None:
-                return out
+        name = name if name is not None else (batch["name"][0] if batch is not None and "name" in batch else "sample")
         stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale)
-        prev = stepper.unet.cache_attn_maps
+        mid = (len(sig) - 1) // 2
         for i in self.get_sigma_gen(len(sig), init_step=init_step):
-            stepper.step(x, sig[i], sig[i + 1], emit_maps=False)
-        stepper.unet.cache_attn_maps = prev
+            stepper.step(x, sig[i], sig[i + 1], emit_maps=(i == mid))
+            if i == mid:
+                attn_map = stepper.unet.save_attn_map(save_name=name, tokens=batch["label"][0])
+                self.save_segment_map(attn_map, tokens=batch["label"][0], save_name=name)
         stepper.check()
         return x
 
@@ -533,209 +832,6 @@ class EulerEDMSampler(EDMSampler):
             pass
         return x
 
-    # ------------------------------------------------------------------------------- batches in flight
-    def sample_in_flight(self, model, xs, conds, ucs, init_step=0, deferred_checks: Optional[list] = None,
-                         streams: Optional[list] = None):
-        """run the sampling loops of SEVERAL independent batches concurrently (one launch stream + one set of
-        hipGraphs each, every stream planned for its share of the CUs) and return their latents.
-
-        One launch stream cannot keep the chip busy through every kernel's ramp-up, epilogue and tail; measured on
-        MI355X (512x512, batch 4): 14.0 ms per sampler step for one batch at a time, 10.9 ms per step and batch with
-        two batches in flight, 10.1 with three (pipeline.IN_FLIGHT).  Falls back to one batch after the other when
-        graphs are unavailable.
-
-        ``deferred_checks``: a list that receives the runners' error-word checks instead of running them here (each
-        check synchronises its stream) — a caller that keeps enqueuing work behind this call (pipeline.predict_many)
-        runs them once at its own synchronisation point.
-        ``streams``: launch streams to replay on, one per batch (default: the runners' capture streams).  A caller
-        that already owns one stream per batch passes them so that no further streams are active: hipStreams share a
-        small number of hardware queues (GPU_MAX_HW_QUEUES, 4 by default) and two busy streams on one queue serialise."""
-        n = len(xs)
-        if n == 1 or not self.use_graphs:
-            return [self(model, x, cond=c, uc=u, init_step=init_step) for x, c, u in zip(xs, conds, ucs)]
-        self._check_fast_path()
-        sig = self._host_sigmas(None)
-        steps = list(self.get_sigma_gen(len(sig), init_step=init_step))
-        cache = self.__dict__.setdefault("_in_flight", {})
-        fp = weights_fingerprint(model)
-        runners = []
-        for slot, (x, c, u) in enumerate(zip(xs, conds, ucs)):
-            require_gpu(x, "EulerEDMSampler")
-            u = default(u, c)
-            key = (slot, n, id(model), tuple(x.shape), len(sig), float(self.guider.scale), tuple(sig[:2]), x.device.index)
-            gs = cache.get(key)
-            if gs is not None and gs.fingerprint != fp:        # weights changed: the captured pointers are stale
-                cache.pop(key)
-                gs = None
-            if gs is None or not gs.rebind(c, u):
-                gs = _GraphedSteps(model, c, u, x.shape[0], x.shape[2:], self.guider.scale, sig, cu_share=n)
-                cache.pop(key, None)
-                while len(cache) >= 6:                      # every runner owns a memory pool: keep the newest few
-                    cache.pop(next(iter(cache)))
-                cache[key] = gs
-            gs.x.copy_(x.float())
-            gs.x.mul_((1.0 + sig[0] ** 2.0) ** 0.5)
-            for i in steps:
-                if i not in gs.graphs:
-                    gs._capture(i)
-            runners.append(gs)
-        main = torch.cuda.current_stream()
-        lanes = list(streams[:n]) if streams is not None and len(streams) >= n else [gs.capture_stream for gs in runners]
-        for lane in lanes:
-            lane.wait_stream(main)
-        for i in steps:                                  # interleaved launches: every queue stays fed
-            for gs, lane in zip(runners, lanes):
-                with torch.cuda.stream(lane):
-                    gs.graphs[i].replay()
-        for lane in lanes:
-            main.wait_stream(lane)
-        outs = [gs.x.clone() for gs in runners]
-        for gs in runners:
-            if deferred_checks is not None:
-                deferred_checks.append(gs.st.check)
-            else:
-                gs.st.check()
-        return outs
-
-    def sample_lane(self, model, x, cond, uc, slot: int, n_lanes: int, init_step=0, deferred_checks: Optional[list] = None):
-        """the sampling loop of ONE batch on the CURRENT stream, as lane ``slot`` of ``n_lanes`` free-running lanes
-        (pipeline.predict_many): rebind this lane's runner to the batch, enqueue all graph replays, return the latent — no
-        host synchronisation and no event shared with the other lanes, so a lane runs condition -> sample -> decode back to
-        back while the launch thread is already feeding the next lane.  Launches are planned for 1 / n_lanes of the CUs
-        (cu_share), as in ``sample_in_flight``.  The runner's error-word check goes to ``deferred_checks``."""
-        if n_lanes <= 1 or not self.use_graphs:
-            return self(model, x, cond=cond, uc=uc, init_step=init_step)
-        self._check_fast_path()
-        require_gpu(x, "EulerEDMSampler")
-        uc = default(uc, cond)
-        sig = self._host_sigmas(None)
-        steps = list(self.get_sigma_gen(len(sig), init_step=init_step))
-        cache = self.__dict__.setdefault("_in_flight", {})
-        fp = weights_fingerprint(model)
-        key = (slot, n_lanes, id(model), tuple(x.shape), len(sig), float(self.guider.scale), tuple(sig[:2]), x.device.index)
-        # a runner that leaves the cache may still have graph replays queued on a lane stream (nothing here synchronises the host):
-        # it is parked in ``_retired`` — its graphs and private memory pool stay alive — until the caller has synchronised
-        # (pipeline.predict_many -> release_retired); runners of the current call's lanes are never evicted
-        # Bounded without the caller's help too (round 6): every runner records an event behind its last replay; parked runners whose
-        # event has completed are dropped on the next call — a caller that uses sample_lane directly, or an exception between eviction
-        # and release, no longer keeps retired hipGraphs and their memory pools alive indefinitely.
-        retired = self.__dict__.setdefault("_retired", [])
-        retired[:] = [r for r in retired if getattr(r, "last_replay", None) is not None and not r.last_replay.query()]
-        gs = cache.get(key)
-        if gs is not None and gs.fingerprint != fp:            # weights changed: the captured pointers are stale
-            retired.append(cache.pop(key))
-            gs = None
-        if gs is None or not gs.rebind(cond, uc):
-            gs = _GraphedSteps(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale, sig, cu_share=n_lanes)
-            if key in cache:
-                retired.append(cache.pop(key))
-            victims = [k for k in cache if not (k[1] == n_lanes and k[2] == id(model) and k[3] == tuple(x.shape))]
-            while len(cache) >= 8 and victims:                  # every runner owns a memory pool: keep the newest few
-                retired.append(cache.pop(victims.pop(0)))
-            cache[key] = gs
-        lane = torch.cuda.current_stream()
-        missing = [i for i in steps if i not in gs.graphs]
-        if missing:
-            # first use of this lane / shape: capture on the runner's own stream (a capture synchronises the device once)
-            gs.capture_stream.wait_stream(lane)
-            for i in missing:
-                gs._capture(i)
-            lane.wait_stream(gs.capture_stream)
-        gs.x.copy_(x.float())
-        gs.x.mul_((1.0 + sig[0] ** 2.0) ** 0.5)
-        for i in steps:
-            gs.graphs[i].replay()
-        out = gs.x.clone()
-        gs.last_replay = torch.cuda.Event()
-        gs.last_replay.record(lane)
-        if deferred_checks is not None:
-            if gs.st.check not in deferred_checks:
-                deferred_checks.append(gs.st.check)
-        else:
-            gs.st.check()
-        return out
-
-    def release_retired(self) -> None:
-        """drop the runners sample_lane took out of its cache — call after the lanes' streams have been synchronised"""
-        self.__dict__.get("_retired", []).clear()
-
-    def _run_graphed(self, model, x, cond, uc, sig, init_step):
-        """replay (capturing on first use) the hipGraphs of this sampling configuration; None -> eager launches"""
-        key = (id(model), tuple(x.shape), len(sig), float(self.guider.scale), tuple(sig[:2]), x.device.index)
-        cache = self.__dict__.setdefault("_graphed", {})
-        try:
-            gs = cache.get(key)
-            if gs is not None and gs.fingerprint != weights_fingerprint(model):
-                gs = None                                       # weights changed under the captured graphs
-            if gs is None or not gs.rebind(cond, uc):
-                cache.clear()                                   # one configuration at a time (each holds a memory pool)
-                gs = _GraphedSteps(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale, sig)
-                cache[key] = gs
-            return gs.run(x, self.get_sigma_gen(len(sig), init_step=init_step))
-        except RuntimeError as e:
-            if not _is_capture_failure(e):                      # kernel status errors, OOM, ...: never hidden
-                raise
-            if not self.__dict__.get("_graph_warned"):
-                print(f"[udifftext_amd] hipGraph capture unavailable ({e}); using eager launches", file=sys.stderr)
-                self._graph_warned = True
-            self.use_graphs = False
-            cache.clear()
-            return None
-
-    def invalidate_graphs(self) -> None:
-        """drop every captured hipGraph (explicit hook; the caches also notice changed weights by fingerprint)"""
-        self.__dict__.pop("_graphed", None)
-        self.__dict__.pop("_in_flight", None)
-
-
-# ================================================================================================ the other samplers
-# HeunEDMSampler, EulerAncestralSampler, DPMPP2SAncestralSampler and DPMPP2MSampler (reference sampling.py:140-215,
-# 423-567).  Every UNet evaluation of any of them is ONE udt_cfg_sampler_step launch after the UNet call:
-#     den  = CFG(xin + c_out*eps_u, xin + c_out*eps_c)                  (c_out = -quantised sigma)
-#     xout = kx*xin + kd*den + ka*aux + kp*prev + kn*noise
-# A sampler only supplies its per-step ``plan``: the evaluations of step i with their sigma and float64 host coefficients, over
-# four named fp32 NCHW buffers — "x" (the latent), "t" (Euler predictor / midpoint) and "h0" / "h1" (denoised history).  The same
-# plan runs as eager launches, inside one hipGraph per (step index, plan), or (tests) as plain torch arithmetic.
-
-
-class Eval(NamedTuple):
-    """one UNet evaluation + its fused update: out = kx*src + kd*den(src, sigma) + ka*aux + kp*prev + kn*noise[step]"""
-    sigma: float                       # UNQUANTISED sigma of the call (c_in, c_out and the timestep use its quantised value)
-    src: str
-    out: str
-    kx: float = 0.0
-    kd: float = 0.0
-    aux: Optional[str] = None
-    ka: float = 0.0
-    prev: Optional[str] = None
-    kp: float = 0.0
-    kn: float = 0.0
-    den_out: Optional[str] = None
-
-
-class MultistepEval(NamedTuple):
-    """one UNet evaluation + the fused linear-multistep update (udt_cfg_multistep_step): d = (src - den(src, sigma))/sigma;
-    out = src + (k0*d + k_1*hist_1 + ...) over ``hist`` = ((buffer, k), ...), the older derivatives newest first; d_out <- d"""
-    sigma: float                       # UNQUANTISED sigma (to_d); c_in, c_out and the timestep use its quantised value
-    src: str
-    out: str
-    d_out: str
-    k0: float
-    hist: tuple = ()
-
-
-def plan_buffers(plans) -> list:
-    """the names of the buffers ``plans`` ((step, plan) pairs) read or write, besides the latent "x", in first-use order"""
-    names = []
-    for _, plan in plans:
-        for e in plan:
-            if isinstance(e, MultistepEval):
-                used = (e.src, e.out, e.d_out) + tuple(b for b, _ in e.hist)
-            else:
-                used = (e.src, e.out, e.aux, e.prev, e.den_out)
-            names.extend(b for b in used if b and b != "x" and b not in names)
-    return names
-
 
 def ancestral_step(sigma: float, sigma_next: float, eta: float):
     """reference sampling_utils.get_ancestral_step in float64 -> (sigma_down, sigma_up)"""
@@ -749,241 +845,6 @@ def _euler_to(sigma: float, target: float):
     """x + (x - den)/sigma * (target - sigma) as (kx, kd)"""
     r = (target - sigma) / sigma
     return 1.0 + r, -r
-
-
-class _GraphedPlan(_GraphedSteps):
-    """hipGraph replay of a plan-driven sampler: one graph per (step index, plan); besides the latent, the scratch / history
-    buffers and the run's ancestral noise ([steps, B, 4, h, w], refreshed per run) are static.  Buffers a plan names beyond
-    "t" / "h0" / "h1" are allocated before its capture"""
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        self.bufs = {"x": self.x}
-        for k in ("t", "h0", "h1"):
-            self.bufs[k] = torch.zeros_like(self.x)
-        self.noise = torch.zeros((len(self.sig) - 1,) + tuple(self.x.shape), dtype=torch.float32, device=self.st.dev)
-
-    def load(self, x: torch.Tensor, noise: Optional[torch.Tensor], init_step: int) -> None:
-        self.x.copy_(x)
-        if noise is not None:
-            self.noise[init_step:].copy_(noise)
-
-    def capture_plan(self, i: int, plan) -> None:
-        st = self.st
-        for name in plan_buffers([(i, plan)]):              # e.g. LinearMultistepSampler's derivative ring d0 .. d{order-1}
-            if name not in self.bufs:
-                self.bufs[name] = torch.zeros_like(self.x)
-        for e in plan:
-            st.emb_rows(st.quantise(e.sigma)[0])             # time-embedding rows are cached outside the graph
-        if not self.warm:
-            torch.cuda.synchronize()
-            with torch.cuda.stream(self.capture_stream):
-                keep = {k: v.clone() for k, v in self.bufs.items()}
-                st.run_plan(self.bufs, plan, self.noise[i])
-                for k, v in keep.items():
-                    self.bufs[k].copy_(v)
-            torch.cuda.synchronize()
-            self.warm = True
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self.pool, stream=self.capture_stream, capture_error_mode="thread_local"):
-            st.run_plan(self.bufs, plan, self.noise[i])
-        self.graphs[(i, plan)] = g
-
-
-class _PlanSampler:
-    """the sampling loop of the plan-driven samplers: __call__, the noise-search initial noise (shared with EulerEDMSampler:
-    it does not depend on the sampler), hipGraph replay, and the lanes of pipeline.predict_many / sample_in_flight"""
-    use_graphs = os.environ.get("UDT_GRAPHS", "1") != "0"
-    uses_noise = False                 # ancestral samplers: one rng draw [B,4,h,w] per step, the last step included
-
-    get_init_noise = EulerEDMSampler.get_init_noise
-    _host_sigmas = EulerEDMSampler._host_sigmas
-    release_retired = EulerEDMSampler.release_retired
-    invalidate_graphs = EulerEDMSampler.invalidate_graphs
-
-    def step_plan(self, sig, i: int, init_step: int = 0) -> tuple:
-        """the evaluations of step i (sig: host sigmas, len num_steps + 1) -> tuple of Eval"""
-        raise NotImplementedError
-
-    def _check_fast_path(self):
-        if not isinstance(self.guider, VanillaCFG):
-            raise NotImplementedError("the fused MI355X step implements VanillaCFG guidance")
-        if getattr(self, "s_churn", 0.0) != 0.0:
-            raise NotImplementedError("s_churn > 0 (stochastic sampling) is not implemented for the fused samplers")
-
-    def _check_options(self, aae_enabled, detailed):
-        if aae_enabled:
-            raise NotImplementedError(f"attend-and-excite is implemented for EulerEDMSampler only, not {type(self).__name__}")
-        if detailed:
-            raise NotImplementedError(f"detailed attention-map dumps are implemented for EulerEDMSampler only, not {type(self).__name__}")
-
-    def draw_step_noise(self, shape, device, num_steps=None, init_step: int = 0) -> Optional[torch.Tensor]:
-        """the ancestral draws of one run: one rng.randn of ``shape`` per step from init_step on, in step order, as ONE device
-        buffer [steps, *shape] (None for the deterministic samplers).  Drawn up front so that graph replays can read a slice
-        per step; the values equal per-step draws because the CPU streams are sequential."""
-        if not self.uses_noise:
-            return None
-        n = len(self._host_sigmas(num_steps)) - 1 - init_step
-        return rng.randn_steps_on(n, shape, device)
-
-    def plans(self, sig, init_step: int = 0):
-        return [(i, self.step_plan(sig, i, init_step)) for i in self.get_sigma_gen(len(sig), init_step=init_step)]
-
-    # --------------------------------------------------------------------------------------------- loop
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, init_step=0, batch=None, aae_enabled=False, detailed=False,
-                 name=None, noise: Optional[torch.Tensor] = None, **kwargs):
-        """reference __call__(denoiser, x, cond, uc, num_steps) [+ init_step]; ``noise``: the run's ancestral draws
-        (draw_step_noise), drawn here when not given"""
-        self._check_options(aae_enabled, detailed)
-        self._check_fast_path()
-        require_gpu(x, type(self).__name__)
-        model = denoiser
-        uc = default(uc, cond)
-        sig = self._host_sigmas(num_steps)
-        x = x.float().contiguous()
-        if noise is None:
-            noise = self.draw_step_noise(x.shape, x.device, num_steps, init_step)
-        x *= (1.0 + sig[0] ** 2.0) ** 0.5
-        plans = self.plans(sig, init_step)
-        if self.use_graphs:
-            out = self._run_graphed(model, x, cond, uc, sig, init_step, plans, noise)
-            if out is not None:
-                return out
-        stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale)
-        bufs = {"x": x, "t": torch.empty_like(x), "h0": torch.empty_like(x), "h1": torch.empty_like(x)}
-        for name in plan_buffers(plans):
-            bufs.setdefault(name, torch.empty_like(x))
-        for i, plan in plans:
-            stepper.run_plan(bufs, plan, noise[i - init_step] if noise is not None else None)
-        stepper.check()
-        return x
-
-    def _run_graphed(self, model, x, cond, uc, sig, init_step, plans, noise):
-        key = (id(model), tuple(x.shape), len(sig), float(self.guider.scale), tuple(sig[:2]), x.device.index)
-        cache = self.__dict__.setdefault("_graphed", {})
-        try:
-            gs = cache.get(key)
-            if gs is not None and gs.fingerprint != weights_fingerprint(model):
-                gs = None
-            if gs is None or not gs.rebind(cond, uc):
-                cache.clear()
-                gs = _GraphedPlan(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale, sig)
-                cache[key] = gs
-            gs.load(x, noise, init_step)
-            for i, plan in plans:
-                g = gs.graphs.get((i, plan))
-                if g is None:
-                    gs.capture_plan(i, plan)
-                    g = gs.graphs[(i, plan)]
-                g.replay()
-            out = gs.x.clone()
-            gs.st.check()
-            return out
-        except RuntimeError as e:
-            if not _is_capture_failure(e):
-                raise
-            if not self.__dict__.get("_graph_warned"):
-                print(f"[udifftext_amd] hipGraph capture unavailable ({e}); using eager launches", file=sys.stderr)
-                self._graph_warned = True
-            self.use_graphs = False
-            cache.clear()
-            return None
-
-    # ------------------------------------------------------------------------------- batches in flight
-    def _lane_runner(self, model, x, cond, uc, slot, n_lanes, sig, plans, retired):
-        """this lane's graph runner, rebound to the batch, with every graph of ``plans`` captured"""
-        cache = self.__dict__.setdefault("_in_flight", {})
-        fp = weights_fingerprint(model)
-        key = (slot, n_lanes, id(model), tuple(x.shape), len(sig), float(self.guider.scale), tuple(sig[:2]), x.device.index)
-        gs = cache.get(key)
-        if gs is not None and gs.fingerprint != fp:            # weights changed: the captured pointers are stale
-            retired.append(cache.pop(key))
-            gs = None
-        if gs is None or not gs.rebind(cond, uc):
-            gs = _GraphedPlan(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale, sig, cu_share=n_lanes)
-            if key in cache:
-                retired.append(cache.pop(key))
-            victims = [k for k in cache if not (k[1] == n_lanes and k[2] == id(model) and k[3] == tuple(x.shape))]
-            while len(cache) >= 8 and victims:                  # every runner owns a memory pool: keep the newest few
-                retired.append(cache.pop(victims.pop(0)))
-            cache[key] = gs
-        missing = [(i, p) for i, p in plans if (i, p) not in gs.graphs]
-        if missing:
-            lane = torch.cuda.current_stream()
-            gs.capture_stream.wait_stream(lane)
-            for i, p in missing:
-                gs.capture_plan(i, p)
-            lane.wait_stream(gs.capture_stream)
-        return gs
-
-    def sample_lane(self, model, x, cond, uc, slot: int, n_lanes: int, init_step=0, deferred_checks: Optional[list] = None,
-                    noise: Optional[torch.Tensor] = None):
-        """EulerEDMSampler.sample_lane for this sampler: the loop of ONE batch on the CURRENT stream as lane ``slot`` of
-        ``n_lanes``, no host synchronisation; ``noise``: the batch's ancestral draws (drawn here when not given)"""
-        if n_lanes <= 1 or not self.use_graphs:
-            return self(model, x, cond=cond, uc=uc, init_step=init_step, noise=noise)
-        self._check_fast_path()
-        require_gpu(x, type(self).__name__)
-        uc = default(uc, cond)
-        sig = self._host_sigmas(None)
-        if noise is None:
-            noise = self.draw_step_noise(x.shape, x.device, None, init_step)
-        plans = self.plans(sig, init_step)
-        retired = self.__dict__.setdefault("_retired", [])
-        retired[:] = [r for r in retired if getattr(r, "last_replay", None) is not None and not r.last_replay.query()]
-        gs = self._lane_runner(model, x, cond, uc, slot, n_lanes, sig, plans, retired)
-        lane = torch.cuda.current_stream()
-        gs.load(x.float(), noise, init_step)
-        gs.x.mul_((1.0 + sig[0] ** 2.0) ** 0.5)
-        for i, p in plans:
-            gs.graphs[(i, p)].replay()
-        out = gs.x.clone()
-        gs.last_replay = torch.cuda.Event()
-        gs.last_replay.record(lane)
-        if deferred_checks is not None:
-            if gs.st.check not in deferred_checks:
-                deferred_checks.append(gs.st.check)
-        else:
-            gs.st.check()
-        return out
-
-    def sample_in_flight(self, model, xs, conds, ucs, init_step=0, deferred_checks: Optional[list] = None,
-                         streams: Optional[list] = None, noises: Optional[list] = None):
-        """EulerEDMSampler.sample_in_flight for this sampler: several independent batches, one launch stream each, graph
-        replays interleaved step by step; ``noises[k]``: batch k's ancestral draws (drawn here, in batch order, when not given)"""
-        n = len(xs)
-        if noises is None:
-            noises = [self.draw_step_noise(x.shape, x.device, None, init_step) for x in xs]
-        if n == 1 or not self.use_graphs:
-            return [self(model, x, cond=c, uc=u, init_step=init_step, noise=nz) for x, c, u, nz in zip(xs, conds, ucs, noises)]
-        self._check_fast_path()
-        sig = self._host_sigmas(None)
-        plans = self.plans(sig, init_step)
-        retired = self.__dict__.setdefault("_retired", [])
-        main = torch.cuda.current_stream()
-        runners = []
-        for slot, (x, c, u, nz) in enumerate(zip(xs, conds, ucs, noises)):
-            require_gpu(x, type(self).__name__)
-            gs = self._lane_runner(model, x, c, default(u, c), slot, n, sig, plans, retired)
-            gs.load(x.float(), nz, init_step)
-            gs.x.mul_((1.0 + sig[0] ** 2.0) ** 0.5)
-            runners.append(gs)
-        lanes = list(streams[:n]) if streams is not None and len(streams) >= n else [gs.capture_stream for gs in runners]
-        for lane in lanes:
-            lane.wait_stream(main)
-        for i, p in plans:                               # interleaved launches: every queue stays fed
-            for gs, lane in zip(runners, lanes):
-                with torch.cuda.stream(lane):
-                    gs.graphs[(i, p)].replay()
-        for lane in lanes:
-            main.wait_stream(lane)
-        outs = [gs.x.clone() for gs in runners]
-        for gs in runners:
-            if deferred_checks is not None:
-                deferred_checks.append(gs.st.check)
-            else:
-                gs.st.check()
-        return outs
 
 
 class HeunEDMSampler(_PlanSampler, EDMSampler):
