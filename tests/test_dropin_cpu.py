@@ -72,7 +72,7 @@ def test_full_key_set_safetensors_round_trip(small_engine, tmp_path):
     assert fresh.init_from_ckpt(ck) == ([], [])
 
 
-def test_prepare_packs_dedups_and_frees(small_engine):
+def test_prepare_builds_layouts_dedups_and_frees(small_engine):
     from sgm.modules import hipnn as H
     from sgm.util import instantiate_from_config
     eng = instantiate_from_config(small_model_config().model)
@@ -107,8 +107,8 @@ def test_prepare_packs_dedups_and_frees(small_engine):
     # packed layouts exist for every evaluated module; fused children were not packed on their own
     blk = eng.model.diffusion_model.input_blocks[1][1].transformer_blocks[0]
     # the LayerNorm-folded layouts serve attn1 / GEGLU (UDT_LN_GEMM, default on): prepare() packs THOSE, not the plain ones
-    assert H.LN_GEMM and getattr(blk.attn1, "_pkln", None) is not None and getattr(blk.attn1, "_pk", None) is None
-    assert getattr(blk.attn1.to_q, "_pk", None) is None
+    assert H.LN_GEMM and H.has_layout(blk.attn1, "ln") and not H.has_layout(blk.attn1, "plain")
+    assert not H.has_layout(blk.attn1.to_q, "plain")
     wf, c_ln, s_ln = blk.attn1.packed_ln(blk.norm1)
     ref_f = (torch.cat([blk.attn1.to_q.weight, blk.attn1.to_k.weight, blk.attn1.to_v.weight]) * blk.norm1.weight[None, :]).to(torch.bfloat16)
     assert torch.equal(wf, ref_f) and c_ln.shape[0] == wf.shape[0] == s_ln.shape[0]

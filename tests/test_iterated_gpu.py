@@ -150,7 +150,7 @@ def _aae_run(env, engine, graph: bool, *args, **kw):
 
 
 # ------------------------------------------------------------------------------------------------ the backward layouts' cache
-def test_backward_layouts_live_and_die_with_their_module(env):
+def test_backward_layouts_follow_the_weights_and_die_with_their_module(env):
     """backward.linear_bwd / conv_bwd on a hipnn.Linear and a 3x3 hipnn.Conv2d; both freed; same-shaped modules with DIFFERENT weights
     built in the same order (CPython may hand out the same id(), the caching allocator the same pointers, and the weights carry equal
     version counts): their backward-data must follow the new weights.  No backward layout outlives its module."""
@@ -184,7 +184,6 @@ def test_backward_layouts_live_and_die_with_their_module(env):
             f"{key1[1::2] == key2[1::2]}")
     gc.collect()
     assert all(r() is None for r in refs1 + refs2), "a backward layout outlived its module"
-    env.bw.clear_cache()                                                   # (kept for existing callers)
 
 
 # ------------------------------------------------------------------------------------------------ G15a: the loop and its exits

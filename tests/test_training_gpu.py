@@ -284,12 +284,13 @@ def test_training_gradients_at_512_vs_oracle_autograd(engine, env):
     assert rel <= TOL_STEP and worst[0] <= 3 * TOL_STEP, (rel, worst)
 
 
-def test_training_step_updates_only_the_trained_parameters(engine, env):
+def test_training_step_updates_trained_parameters_and_their_layouts(engine, env):
     """training.training_step: gradients -> AdamW on the t_attn / t_norm masters; every other parameter untouched; the packed layouts
     and the graph fingerprint notice — the second step's loss through the warm caches equals the same loss from cold caches bit for
     bit; the same step from the same state is bit-reproducible"""
     import copy
     from aae_fixture import train_batch
+    from sgm.modules import hipnn as H
     from sgm.modules.diffusionmodules.sampling import weights_fingerprint
     g = np.load(os.path.join(GOLD, "train_golden.npz"))
     dev = env.dev
@@ -320,11 +321,7 @@ def test_training_step_updates_only_the_trained_parameters(engine, env):
     # the step-2 loss through the caches step 1 left behind must equal the same loss from COLD caches (every packed layout of the
     # forward, the backward layouts, the time-embedding rows rebuilt from the masters): bit for bit — same kernels, same inputs
     ld2w, _ = tr.training_loss_and_grads(engine, z, cond, seg, segm, sigma_idx=idx, noise=noise, want_grads=False)
-    for m in engine.modules():
-        for a in ("_pk_key", "_pk8_key", "_pkln_key", "_pkln8_key", "_pkfp_key") + (("_emb_key",) if hasattr(m, "_emb_w") else ()):
-            if getattr(m, a, None) is not None:
-                setattr(m, a, None)
-    env.bw.clear_cache()
+    H.drop_layouts(engine)
     ld2c, _ = tr.training_loss_and_grads(engine, z, cond, seg, segm, sigma_idx=idx, noise=noise, want_grads=False)
     for k in ("loss/diff_loss", "loss/full_loss"):
         assert torch.equal(ld2w[k], ld2c[k]), (k, float(ld2w[k]), float(ld2c[k]))

@@ -18,48 +18,19 @@ torch is used for memory only (allocation, views, channel concatenation / split,
 """
 from __future__ import annotations
 
-import weakref
 from typing import Callable, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
+from sgm.modules import hipnn as H
 
 from . import ops, packing
 
 Bwd = Callable[[Optional[torch.Tensor]], Optional[torch.Tensor]]
-DEBUG_SUMS: Optional[list] = None       # (tools/debug_train3.py: per-layer checksums of the tape-mode forward)
-
-# the backward layouts (W^T of every linear, the flipped 3x3 taps, the fused wqkvT) of each module: {module: {tag: (key, layout)}}.
-# Keyed by the module object itself, weakly: a freed engine's layouts die with it, and a new module that happens to get the same
-# id() (and weights at reused pointers with equal version counts) cannot hit them.  Validated like _Packed.packed() by _key()
-# (data_ptr, _version, device); writes through ``p.data`` do not bump _version, so neither cache sees them.
-_CACHE: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-
-
-def _cached(mod, tag: str, build):
-    ver = mod._key()
-    per_mod = _CACHE.get(mod)
-    if per_mod is None:
-        per_mod = _CACHE[mod] = {}
-    hit = per_mod.get(tag)
-    if hit is None or hit[0] != ver:
-        with torch.no_grad():
-            hit = (ver, build())
-        per_mod[tag] = hit
-    return hit[1]
-
-
-def clear_cache() -> None:
-    _CACHE.clear()
-
-
-def _need_masters(mod) -> None:
-    if getattr(mod, "_pk_frozen", False):
-        raise ops.L.UdtError("attend-and-excite needs the fp32 master weights for the backward layouts: build the engine without "
-                             "prepare(free_masters=True)")
 
 
 # ------------------------------------------------------------------------------------------------ linear / convolution
+# (the backward layouts — W^T of every linear, the flipped 3x3 taps, the fused wqkvT — are layouts of their modules, hipnn.layout)
 def linear_bwd(lin, dy: torch.Tensor, add: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dX = dY W (+ add): the forward GEMM on W^T packed as [in_features, out_features]"""
     return ops.linear(dy, _linear_wt(lin), None, residual=add)
@@ -67,15 +38,13 @@ def linear_bwd(lin, dy: torch.Tensor, add: Optional[torch.Tensor] = None) -> tor
 
 def _linear_wt(lin) -> torch.Tensor:
     """backward-data weights of a linear: W^T packed as [in_features, out_features]"""
-    _need_masters(lin)
-    return _cached(lin, "wT", lambda: packing.pack_linear(lin.weight.detach().t().contiguous()))
+    return H.layout(lin, "wT", lambda: packing.pack_linear(lin.weight.detach().t().contiguous()))
 
 
 def _conv_wt(conv, n_pad: int = 4) -> torch.Tensor:
     """backward-data weights of a convolution: Wb[ci, co, ky, kx] = W[co, ci, k - 1 - ky, k - 1 - kx], packed like a forward conv
     that reads ``out_channels`` channels and writes ``in_channels``"""
-    _need_masters(conv)
-    return _cached(conv, f"wT{n_pad}", lambda: packing.pack_conv(conv.weight.detach().flip(2, 3).permute(1, 0, 2, 3).contiguous(), None, n_pad))
+    return H.layout(conv, f"wT{n_pad}", lambda: packing.pack_conv(conv.weight.detach().flip(2, 3).permute(1, 0, 2, 3).contiguous(), None, n_pad))
 
 
 def conv_bwd(conv, dy: torch.Tensor, add: Optional[torch.Tensor] = None, n_pad: int = 4) -> torch.Tensor:
@@ -207,8 +176,7 @@ def transformer_block_fwd(blk, t1: torch.Tensor, B: int, kv: torch.Tensor, rec: 
         d_t2 = ops.layer_norm_bwd(t2, d_n2, blk.t_norm.weight, blk.t_norm.eps, add=d_t3)
         d_o = linear_bwd(a1.to_out[0], d_t2).reshape(B, N, Cc)
         d_qkv = ops.attention_bwd(qkv, o, d_o, heads, scale)
-        _need_masters(a1.to_q)
-        wqkv_t = _cached(a1, "wqkvT", lambda: packing.pack_linear(
+        wqkv_t = H.layout(a1, "wqkvT", lambda: packing.pack_linear(
             torch.cat([a1.to_q.weight, a1.to_k.weight, a1.to_v.weight], 0).detach().t().contiguous()))
         d_n1 = ops.linear(d_qkv.reshape(M, 3 * Cc), wqkv_t, None)
         return ops.layer_norm_bwd(t1, d_n1, blk.norm1.weight, blk.norm1.eps, add=d_t2)
@@ -244,7 +212,6 @@ def _block_fwd(unet, block, prefix: str, h: torch.Tensor, emb_rows: torch.Tensor
     """one TimestepEmbedSequential; returns (out, bwd) with bwd(d_out) -> (d_in, d_x2)"""
     from sgm.modules.attention import SpatialTransformer
     from sgm.modules.diffusionmodules.openaimodel import Downsample, ResBlock, Upsample
-    from sgm.modules import hipnn as H
     bwds = []
     for j, layer in enumerate(block):
         if isinstance(layer, ResBlock):
@@ -270,8 +237,6 @@ def _block_fwd(unet, block, prefix: str, h: torch.Tensor, emb_rows: torch.Tensor
             bwds.append(("lin", lambda d, c=layer: conv_bwd(c, d, n_pad=64) if d is not None else None))
         else:
             raise NotImplementedError(type(layer).__name__)
-        if DEBUG_SUMS is not None:
-            DEBUG_SUMS.append((f"{prefix}{j}", float(h.float().abs().sum())))
 
     def bwd(d):
         d_x2 = None
@@ -340,7 +305,7 @@ class UNetTape:
             self.eps = ops.conv2d(a, w, bb, ksize=3, flags=ops.L.GEMM_OUT_F32, n_out=w.shape[0])
             self._head = (h, gn, conv)
 
-    def backward(self, d_eps: Optional[torch.Tensor] = None, param_grads: Optional[dict] = None, debug: Optional[dict] = None):
+    def backward(self, d_eps: Optional[torch.Tensor] = None, param_grads: Optional[dict] = None):
         for it in self.maps:
             it["pgrads"] = param_grads
         d = None
@@ -350,20 +315,12 @@ class UNetTape:
             d = ops.group_norm_bwd(h, d_a, gn.weight, gn.bias, gn.num_groups, gn.eps, True)
         n_in = self.n_in
         d_skips: List[Optional[torch.Tensor]] = [None] * n_in
-        if debug is not None:                                         # (tools/debug_aae.py: maps and block-boundary cotangents)
-            debug["maps"] = self.maps
         for j in reversed(range(len(self.out_tape))):
-            if debug is not None and d is not None:
-                debug[f"d_output_blocks.{j}"] = d.clone()
             d, d_x2 = self.out_tape[j](d)
             d_skips[n_in - 1 - j] = d_x2                              # output block j consumed hs[n_in - 1 - j]
-        if debug is not None and d is not None:
-            debug["d_middle_block"] = d.clone()
         d, _ = self.b_mid(d)
         for i in reversed(range(n_in)):
             d = _acc(d, d_skips[i])
-            if debug is not None and d is not None:
-                debug[f"d_input_blocks.{i}"] = d.clone()
             d, _ = self.tape[i](d)
         if param_grads is not None:
             # blocks the reverse pass never reached (downstream of the last map read, no eps cotangent) have zero gradients
@@ -381,8 +338,8 @@ class UNetTape:
         return d
 
 
-def unet_maps_vjp(unet, x: torch.Tensor, timesteps: torch.Tensor, concat: torch.Tensor, t_context: torch.Tensor, maps_grad,
-                  debug: Optional[dict] = None) -> torch.Tensor:
+def unet_maps_vjp(unet, x: torch.Tensor, timesteps: torch.Tensor, concat: torch.Tensor, t_context: torch.Tensor,
+                  maps_grad) -> torch.Tensor:
     """d F / d x (fp32 [B, 4, h, w]) for a scalar F of the UNet's t_attn probability maps: the tape-mode forward of
     UNet(cat(x, concat)) records every map as a dict (name, heads, size, attn_map fp32 [B * heads, n, L], d_probs None);
     ``maps_grad(maps)`` sets ``d_probs`` = d F / d attn_map on the maps F reads (None elsewhere: those layers, and everything
@@ -391,14 +348,14 @@ def unet_maps_vjp(unet, x: torch.Tensor, timesteps: torch.Tensor, concat: torch.
     xin = ops.nchw_to_nhwc(torch.cat((x.float(), concat.float()), dim=1).contiguous(), CPAD)
     tape = UNetTape(unet, xin, timesteps, t_context, with_head=False)
     maps_grad(tape.maps)
-    d = tape.backward(debug=debug)
+    d = tape.backward()
     if d is None:
         raise ValueError("maps_grad set no d_probs: nothing to differentiate")
     return ops.nhwc_to_nchw(d.contiguous(), 4)
 
 
 def unet_local_loss_grad(unet, loss_fn, x: torch.Tensor, timesteps: torch.Tensor, concat: torch.Tensor, t_context: torch.Tensor,
-                         mask: torch.Tensor, seg_mask: torch.Tensor, debug: Optional[dict] = None):
+                         mask: torch.Tensor, seg_mask: torch.Tensor):
     """(local_loss fp32 [B], d sum(local_loss) / d x fp32 [B, 4, h, w]) for x fp32 NCHW: the UNet sees cat(x, concat) and the
     t_attn maps of size >= loss_fn.min_attn_size are scored by get_min_local_loss (reference sampling.py:233-252, loss.py:192-235)"""
     B = x.shape[0]
@@ -415,7 +372,7 @@ def unet_local_loss_grad(unet, loss_fn, x: torch.Tensor, timesteps: torch.Tensor
             it["d_probs"] = torch.zeros_like(it["attn_map"])
             ops.local_loss_bwd(it["attn_map"], maskf, seg, gk, it["d_probs"], loss, it["heads"], it["size"], 1.0 / len(used))
         count[0] = len(used)
-    grad = unet_maps_vjp(unet, x, timesteps, concat, t_context, maps_grad, debug=debug)
+    grad = unet_maps_vjp(unet, x, timesteps, concat, t_context, maps_grad)
     return loss / count[0], grad
 
 

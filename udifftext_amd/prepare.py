@@ -7,11 +7,14 @@ after load, in a prepare step; §8f rank 3: checkpoint ingestion & weight packin
   ``conditioner.embedders.2.model.*``, loaded from the same file (configs/test/textdesign_sd_2.yaml:70,91;
   sgm/models/diffusion.py:87-105).  When every tensor of the two is equal the LatentEncoder is pointed at
   ``first_stage_model``: one set of masters, one set of packed weights (the state dict keeps both prefixes).
-* **packing** — every module's device layout (bf16, K-contiguous, fused q|k / k|v / GEGLU blocks, the 22 ``emb_layers``
-  as one matrix) is derived now; modules whose weights are consumed only through a parent's fused pack are skipped.
-* **free_masters=True** — the fp32 checkpoint-layout parameters of the packed modules are released (5.4 GB of the
-  engine's 8.1 GB on the device) and the caches are frozen.  The engine then serves inference only: its state dict no
-  longer holds those weights, so reload the checkpoint into a fresh engine to change them.
+* **packing** — every layout the forward pass reads (``hipnn.layout``: bf16 K-contiguous packs, fused q|k|v / k|v / GEGLU
+  blocks, the LayerNorm-folded packs, the ``[W_po W_2 | W_po]`` fold, the 22 ``emb_layers`` as one matrix; with UDT_FP8 the
+  e4m3 packs too) is built now; modules whose weights are consumed only through a parent's fused pack are skipped.
+* **free_masters=True** — then, in one pass, every module that can own layouts is frozen (``hipnn.freeze_layouts``: it
+  serves the layouts it has built and raises UdtError for any other) and the fp32 checkpoint-layout parameters of the
+  packed modules are released (5.4 GB of the engine's 8.1 GB on the device).  The engine then serves inference only — no
+  attend-and-excite, no training: its state dict no longer holds those weights, so reload the checkpoint into a fresh
+  engine to change them or the launch path.
 """
 from __future__ import annotations
 
@@ -64,35 +67,31 @@ def prepare(engine, free_masters: bool = False, dedup_vae: bool = True) -> Dict[
             if id(m) in seen:
                 continue
             seen.add(id(m))
-            pk = m.packed()
             report["packed_modules"] += 1
-            for t in (pk if isinstance(pk, (tuple, list)) else (pk,)):
-                if isinstance(t, torch.Tensor):
-                    report["packed_bytes"] += t.numel() * t.element_size()
-        w, b = unet._emb_pack()
-        report["packed_bytes"] += w.numel() * w.element_size() + b.numel() * b.element_size()
+            report["packed_bytes"] += H.nbytes(m.packed())
+        report["packed_bytes"] += H.nbytes(unet._emb_pack())
         # ---- LayerNorm-folded layouts of the q|k|v and GEGLU projections (udt_ln_gemm_fwd)
         from sgm.modules.attention import BasicTransformerBlock
-        # (in config #5 — UDT_FP8=1 — prepare_ln / prepare_mx8 also build, and freeze, the e4m3 layouts of the blocks whose linears
-        #  run on MX8 operands: ahead of the release of the masters)
+        # (in config #5 — UDT_FP8=1 — prepare_ln / prepare_mx8 also build the e4m3 layouts of the blocks whose linears run on MX8
+        #  operands: ahead of the release of the masters)
         if H.LN_GEMM:
             from sgm.modules.attention import SpatialTransformer
             for m in unet.modules():
                 if isinstance(m, BasicTransformerBlock):
-                    report["packed_bytes"] += m.prepare_ln(freeze=free_masters)
+                    report["packed_bytes"] += m.prepare_ln()
                 elif isinstance(m, SpatialTransformer):
-                    report["packed_bytes"] += m.prepare_mx8(freeze=free_masters)
-                    report["packed_bytes"] += m.prepare_ffproj(freeze=free_masters)      # (round 6: [W_po W_2 | W_po], attention.FF_PROJ)
-        # ---- release the masters
+                    report["packed_bytes"] += m.prepare_mx8()
+                    report["packed_bytes"] += m.prepare_ffproj()      # (round 6: [W_po W_2 | W_po], attention.FF_PROJ)
+        # ---- freeze every module that can own layouts (it serves what it has built), release the masters of the packed ones
         if free_masters:
             victims = []
             for m in engine.modules():
-                if isinstance(m, H._Packed) and (id(m) in seen or id(m) in fused or (id(m) in ln_only and getattr(m, "_pkln_frozen", False))):
-                    m._pk_frozen = True
+                if hasattr(m, "_sources"):
+                    H.freeze_layouts(m)
+                if isinstance(m, H._Packed):
                     victims += list(m.parameters(recurse=False))
                     if hasattr(m, "own_masters"):
                         victims += m.own_masters()
-            unet._emb_frozen = True
             done = set()
             for p in victims:
                 if id(p) in done:

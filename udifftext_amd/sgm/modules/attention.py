@@ -42,8 +42,8 @@ class GEGLU(H._Packed):
         super().__init__()
         self.proj = H.Linear(dim_in, dim_out * 2)
 
-    def _key(self):
-        return self.proj._key()
+    def _sources(self):
+        return self.proj._sources()
 
     def fused_children(self):
         return [self.proj]
@@ -101,8 +101,8 @@ class CrossAttention(H._Packed):
         self.to_out = zero_module(nn.Sequential(H.Linear(inner, query_dim), nn.Identity()))
         self.attn_map_cache = None
 
-    def _key(self):
-        return self.to_k._key() + self.to_v._key()
+    def _sources(self):
+        return self.to_k.weight, self.to_v.weight
 
     def fused_children(self):
         return [self.to_k, self.to_v]
@@ -168,8 +168,8 @@ class MemoryEfficientCrossAttention(H._Packed):
         self.to_v = H.Linear(context_dim, inner, bias=False)
         self.to_out = nn.Sequential(H.Linear(inner, query_dim), nn.Identity())
 
-    def _key(self):
-        return self.to_q._key() + self.to_k._key() + self.to_v._key()
+    def _sources(self):
+        return self.to_q.weight, self.to_k.weight, self.to_v.weight
 
     def fused_children(self):
         return [self.to_q, self.to_k, self.to_v]
@@ -288,29 +288,15 @@ class BasicTransformerBlock(nn.Module):
             return H.carry_mx8(out.reshape(B, N, C), out)
         return self.ff(self.norm3(x2), residual=x2).reshape(B, N, C)
 
-    def prepare_ln(self, freeze: bool = False) -> int:
-        """build (and optionally freeze) the LayerNorm-folded layouts — and, in config #5, the e4m3 layouts of the block's linears
-        (the bf16 ones stay: calls that must return attention maps take the unfused text cross-attention and a bf16 feed-forward);
-        returns their bytes"""
-        n = 0
-        for mod, norm in ((self.attn1, self.norm1), (self.ff.net[0], self.norm3)):
-            for t in mod.packed_ln(norm):
-                n += t.numel() * t.element_size()
-            if freeze:
-                mod._pkln_frozen = True
+    def prepare_ln(self) -> int:
+        """build the LayerNorm-folded layouts — and, in config #5, the e4m3 layouts of the block's linears (the bf16 ones stay:
+        calls that must return attention maps take the unfused text cross-attention and a bf16 feed-forward); returns their bytes"""
+        folded = ((self.attn1, self.norm1), (self.ff.net[0], self.norm3))
+        pks = [mod.packed_ln(norm) for mod, norm in folded]
         if H.mx8_width(self.norm1.dim):
-            for mod, norm in ((self.attn1, self.norm1), (self.ff.net[0], self.norm3)):
-                for t in mod.packed_ln_mx8(norm):
-                    n += t.numel() * t.element_size()
-                if freeze:
-                    mod._pkln8_frozen = True
-            for lin in (self.attn1.to_out[0], self.ff.net[2]):
-                for t in lin.packed_fp8():
-                    if t is not None:
-                        n += t.numel() * t.element_size()
-                if freeze:
-                    lin._pk8_frozen = True
-        return n
+            pks += [mod.packed_ln_mx8(norm) for mod, norm in folded]
+            pks += [lin.packed_fp8() for lin in (self.attn1.to_out[0], self.ff.net[2])]
+        return H.nbytes(*pks)
 
 
 class SpatialTransformer(nn.Module):
@@ -369,38 +355,24 @@ class SpatialTransformer(nn.Module):
                             x8=ops.mx8_of(t) if mx else None)
         return H.carry_stats(out.reshape(B, Hh, Ww, C), out)
 
-    def packed_ffproj(self):
-        """[W_po W_2 | W_po] as a two-source 1x1-convolution weight (bf16 [C, 4 C + C]) and the bias W_po b_2 + b_po; cached by
-        the two modules' parameter versions, frozen by prepare(free_masters=True)"""
-        if getattr(self, "_pkfp_frozen", False):
-            return self._pkfp
+    def _sources(self):
         lin2, po = self.transformer_blocks[-1].ff.net[2], self.proj_out
-        key = (lin2._key(), po._key())
-        if getattr(self, "_pkfp_key", None) != key:
-            with torch.no_grad():
-                w2, wpo = lin2.weight.float(), po.weight.float()
-                wf = torch.cat([wpo @ w2, wpo], dim=1)
-                bias = wpo @ lin2.bias.float() + po.bias.float()
-                self._pkfp = (packing.pack_conv(wf[:, :, None, None], [w2.shape[1], wpo.shape[1]]), packing.pad_bias(bias))
-            self._pkfp_key = key
-        return self._pkfp
+        return lin2.weight, lin2.bias, po.weight, po.bias
 
-    def prepare_ffproj(self, freeze: bool = False) -> int:
-        n = 0
-        if FF_PROJ and H.LN_GEMM:
-            for t in self.packed_ffproj():
-                n += t.numel() * t.element_size()
-            if freeze:
-                self._pkfp_frozen = True
-        return n
+    def _pack_ffproj(self):
+        lin2, po = self.transformer_blocks[-1].ff.net[2], self.proj_out
+        w2, wpo = lin2.weight.float(), po.weight.float()
+        wf = torch.cat([wpo @ w2, wpo], dim=1)
+        bias = wpo @ lin2.bias.float() + po.bias.float()
+        return packing.pack_conv(wf[:, :, None, None], [w2.shape[1], wpo.shape[1]]), packing.pad_bias(bias)
 
-    def prepare_mx8(self, freeze: bool = False) -> int:
+    def packed_ffproj(self):
+        """[W_po W_2 | W_po] as a two-source 1x1-convolution weight (bf16 [C, 4 C + C]) and the bias W_po b_2 + b_po"""
+        return H.layout(self, "ffproj", self._pack_ffproj)
+
+    def prepare_ffproj(self) -> int:
+        return H.nbytes(self.packed_ffproj()) if FF_PROJ and H.LN_GEMM else 0
+
+    def prepare_mx8(self) -> int:
         """config #5: the e4m3 layout of proj_out (proj_in stays a bf16 GEMM: its input is a GroupNorm output); bytes"""
-        n = 0
-        if H.mx8_width(self.proj_in.out_features):
-            for t in self.proj_out.packed_fp8():
-                if t is not None:
-                    n += t.numel() * t.element_size()
-            if freeze:
-                self.proj_out._pk8_frozen = True
-        return n
+        return H.nbytes(self.proj_out.packed_fp8()) if H.mx8_width(self.proj_in.out_features) else 0

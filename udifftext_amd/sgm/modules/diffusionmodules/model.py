@@ -92,8 +92,8 @@ class MemoryEfficientAttnBlock(H._Packed):
         self.v = H.Conv2d(in_channels, in_channels, 1)
         self.proj_out = H.Conv2d(in_channels, in_channels, 1)
 
-    def _key(self):
-        return self.q._key() + self.k._key() + self.v._key() + self.proj_out._key()
+    def _sources(self):
+        return [p for m in (self.q, self.k, self.v, self.proj_out) for p in (m.weight, m.bias)]
 
     def fused_children(self):
         return [self.q, self.k, self.v, self.proj_out]

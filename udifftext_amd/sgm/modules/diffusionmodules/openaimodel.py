@@ -254,16 +254,17 @@ class UnifiedUNetModel(nn.Module):
             pass
         return attn_map_i
 
+    def _sources(self):
+        return [p for rb in self._resblocks for p in (rb.emb_layers[1].weight, rb.emb_layers[1].bias)]
+
+    def _pack_emb(self):
+        lins = [rb.emb_layers[1] for rb in self._resblocks]
+        return (packing.pack_linear(torch.cat([m.weight for m in lins], 0)),
+                torch.cat([m.bias for m in lins], 0).float().contiguous())
+
     def _emb_pack(self):
-        if getattr(self, "_emb_frozen", False):
-            return self._emb_w, self._emb_b
-        key = tuple(rb.emb_layers[1]._key() for rb in self._resblocks)
-        if getattr(self, "_emb_key", None) != key:
-            with torch.no_grad():
-                w = packing.pack_linear(torch.cat([rb.emb_layers[1].weight for rb in self._resblocks], 0))
-                b = torch.cat([rb.emb_layers[1].bias for rb in self._resblocks], 0).float().contiguous()
-            self._emb_w, self._emb_b, self._emb_key = w, b, key
-        return self._emb_w, self._emb_b
+        """every ResBlock's emb_layers Linear stacked into one matrix and one bias"""
+        return H.layout(self, "emb", self._pack_emb)
 
     def time_embedding_rows(self, timesteps: torch.Tensor) -> torch.Tensor:
         """timesteps [B] -> fp32 [B, sum(out_channels of all ResBlocks)]: every block's Linear(SiLU(emb))."""

@@ -218,9 +218,8 @@ class _EncoderLayer(H._Packed):
         self.norm1 = H.LayerNorm(d)
         self.norm2 = H.LayerNorm(d)
 
-    def _key(self):
-        p = self.self_attn.in_proj_weight
-        return ((p.data_ptr(), p._version, str(p.device)),)
+    def _sources(self):
+        return self.self_attn.in_proj_weight, self.self_attn.in_proj_bias
 
     def own_masters(self):
         """parameters consumed only through this module's pack (not Linear / Conv2d children)"""

@@ -115,88 +115,87 @@ def _init_uniform_(p: torch.Tensor, fan_in: int) -> None:
         p.uniform_(-bound, bound)
 
 
-class _Packed(nn.Module):
-    """mixin: cache of repacked device weights, invalidated when parameters move or change.
-    ``fused_children()``: child modules whose weights this module's ``_pack`` consumes (fused q|k|v, ...) — they are never
-    evaluated on their own, so load-time ``prepare`` does not pack them separately.  After ``prepare(free_masters=True)``
-    the cache is frozen (``_pk_frozen``): the fp32 masters are gone and ``packed()`` never looks at them again.
-    Writes through ``p.data`` (``p.data.copy_()``, EMA swaps) do not bump ``_version``: the cache does not see them."""
+class _Layouts(dict):
+    """the derived weight layouts of one module: {tag: (key, layout)}; a frozen store serves what it holds and builds nothing"""
+    frozen = False
 
-    def _key(self):
-        ps = list(self.parameters(recurse=False))
-        return tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
+
+def _layouts(mod: nn.Module) -> _Layouts:
+    store = mod.__dict__.get("_layouts")
+    if store is None:
+        store = mod.__dict__["_layouts"] = _Layouts()
+    return store
+
+
+def layout(mod: nn.Module, tag: str, build, *inputs):
+    """the layout ``tag`` of ``mod``: ``build()`` (under no_grad), kept on ``mod`` and rebuilt only when one of the tensors it
+    reads — ``mod._sources()``, then the tensors among ``inputs`` — changes pointer, version or device, or a non-tensor input
+    changes.  Those tensors are parameters, so weights_fingerprint changes with them and captured graphs recapture.  Writes
+    through ``p.data`` (``p.data.copy_()``, EMA swaps) do not bump ``_version``: neither sees them.  A frozen module
+    (``freeze_layouts``: its fp32 masters are gone) serves the layouts it has built and raises UdtError for any other tag."""
+    store = _layouts(mod)
+    hit = store.get(tag)
+    if store.frozen:
+        if hit is None:
+            raise L.UdtError(f"{type(mod).__name__}: layout {tag!r} was not built before prepare(free_masters=True) released the "
+                             "fp32 masters; reload the checkpoint into a fresh engine to change the launch path")
+        return hit[1]
+    key = [(t.data_ptr(), t._version, t.device) if isinstance(t, torch.Tensor) else t for t in (*mod._sources(), *inputs)]
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            hit = store[tag] = (key, build())
+    return hit[1]
+
+
+def has_layout(mod: nn.Module, tag: str) -> bool:
+    return tag in mod.__dict__.get("_layouts", ())
+
+
+def freeze_layouts(mod: nn.Module) -> None:
+    _layouts(mod).frozen = True
+
+
+def drop_layouts(root: nn.Module) -> None:
+    """forget every layout under ``root`` that is not frozen (the next call rebuilds it from the masters)"""
+    for m in root.modules():
+        store = m.__dict__.get("_layouts")
+        if store is not None and not store.frozen:
+            store.clear()
+
+
+def nbytes(*layouts) -> int:
+    """bytes of the tensors in ``layouts`` (each a tensor, or a tuple of tensors and Nones)"""
+    ts = [t for pk in layouts for t in (pk if isinstance(pk, (tuple, list)) else (pk,))]
+    return sum(t.numel() * t.element_size() for t in ts if isinstance(t, torch.Tensor))
+
+
+class _Packed(nn.Module):
+    """mixin: the layouts (``layout()``) of a module with its own device weights.  ``_sources()``: the tensors its layouts read
+    (default: its own parameters).  ``fused_children()``: child modules whose weights this module's ``_pack`` consumes (fused
+    q|k|v, ...) — they are never evaluated on their own, so load-time ``prepare`` does not pack them separately."""
+
+    def _sources(self):
+        return self._parameters.values()
 
     def fused_children(self):
         return []
 
     def packed(self):
-        if getattr(self, "_pk_frozen", False):
-            if not hasattr(self, "_pk"):
-                raise L.UdtError(f"{type(self).__name__}: prepare(free_masters=True) kept only the LayerNorm-folded layout of this "
-                                 "module (UDT_LN_GEMM on) and released the fp32 masters — the plain layout cannot be built any "
-                                 "more; reload the checkpoint into a fresh engine to change the launch path")
-            return self._pk
-        key = self._key()
-        if getattr(self, "_pk_key", None) != key:
-            with torch.no_grad():
-                self._pk = self._pack()
-            self._pk_key = key
-        return self._pk
-
-    def _pack(self):
-        raise NotImplementedError
+        return layout(self, "plain", self._pack)
 
     def packed_fp8(self):
-        """the fp8 (e4m3 + per-channel scale) layout of the same weights, cached like ``packed()``"""
-        if getattr(self, "_pk8_frozen", False):
-            return self._pk8
-        if getattr(self, "_pk_frozen", False):
-            raise L.UdtError(f"{type(self).__name__}: the fp32 masters were released by prepare(free_masters=True) before the "
-                             "fp8 layout was built — call prepare() with UDT_FP8=1 set (it then packs and freezes the e4m3 "
-                             "layouts too), or reload the checkpoint")
-        key = self._key()
-        if getattr(self, "_pk8_key", None) != key:
-            with torch.no_grad():
-                self._pk8 = self._pack_fp8()
-            self._pk8_key = key
-        return self._pk8
-
-    def _pack_fp8(self):
-        raise NotImplementedError(f"{type(self).__name__} has no fp8 layout")
+        """the fp8 (e4m3 + per-channel scale) layout of the same weights"""
+        return layout(self, "fp8", self._pack_fp8)
 
     def packed_ln(self, norm):
         """the LayerNorm-folded layout (packing.pack_ln_linear) of these weights behind ``norm`` for udt_ln_gemm_fwd:
-        (gamma o W as bf16, c = W beta + bias, s = row sums of the folded weights); cached like ``packed()`` and frozen
-        with it by ``prepare(free_masters=True)``"""
-        if getattr(self, "_pkln_frozen", False):
-            return self._pkln
-        key = (self._key(), norm.weight.data_ptr(), norm.weight._version, norm.bias.data_ptr(), norm.bias._version)
-        if getattr(self, "_pkln_key", None) != key:
-            with torch.no_grad():
-                self._pkln = self._pack_ln(norm.weight, norm.bias)
-            self._pkln_key = key
-        return self._pkln
-
-    def _pack_ln(self, gamma, beta):
-        raise NotImplementedError(f"{type(self).__name__} has no LayerNorm-folded layout")
+        (gamma o W as bf16, c = W beta + bias, s = row sums of the folded weights)"""
+        return layout(self, "ln", lambda: self._pack_ln(norm.weight, norm.bias), norm.weight, norm.bias)
 
     def packed_ln_mx8(self, norm):
         """the LayerNorm-folded layout on e4m3 weights (packing.pack_ln_linear_mx8) for UDT_GEMM_MX8 + ln_colsum: (gamma o W as
-        e4m3, per-channel scales, c, s); cached and frozen like ``packed_ln()``"""
-        if getattr(self, "_pkln8_frozen", False):
-            return self._pkln8
-        if getattr(self, "_pk_frozen", False) and getattr(self, "_pkln8_key", None) is None:
-            raise L.UdtError(f"{type(self).__name__}: the fp32 masters were released by prepare(free_masters=True) before the MX8 "
-                             "layout was built — call prepare() with UDT_FP8=1 set, or reload the checkpoint")
-        key = (self._key(), norm.weight.data_ptr(), norm.weight._version, norm.bias.data_ptr(), norm.bias._version)
-        if getattr(self, "_pkln8_key", None) != key:
-            with torch.no_grad():
-                self._pkln8 = self._pack_ln_mx8(norm.weight, norm.bias)
-            self._pkln8_key = key
-        return self._pkln8
-
-    def _pack_ln_mx8(self, gamma, beta):
-        raise NotImplementedError(f"{type(self).__name__} has no LayerNorm-folded MX8 layout")
+        e4m3, per-channel scales, c, s)"""
+        return layout(self, "ln_mx8", lambda: self._pack_ln_mx8(norm.weight, norm.bias), norm.weight, norm.bias)
 
 
 class Linear(_Packed):
@@ -258,6 +257,9 @@ class Conv2d(_Packed):
     def _pack(self):
         return packing.pack_conv(self.weight, self.segments, self.n_pad), packing.pad_bias(self.bias, self.n_pad)
 
+    def packed(self):
+        return layout(self, "plain", self._pack, self.segments, self.n_pad)
+
     def forward(self, x, x2=None, residual=None, rowvec=None, upsample: bool = False, flags: int = 0,
                 pad: Optional[tuple] = None, out_hw: Optional[tuple] = None, norm: Optional["GroupNorm"] = None,
                 norm_silu: bool = False, colstats: Optional[bool] = None):
@@ -265,12 +267,10 @@ class Conv2d(_Packed):
         the reference's ``GroupNorm32 -> SiLU -> conv`` chains (openaimodel.py:183-187,218-231; model.py:128-148).  Fused
         into the convolution (statistics from the producers' epilogues, scale/shift applied on the staged patch) when
         possible, otherwise the separate GroupNorm kernels run first.  colstats: emit the output's statistics."""
-        if (x2 is not None and self.segments is None and not getattr(self, "_pk_frozen", False)
-                and (x.shape[-1] % 64 != 0 or x2.shape[-1] % 64 != 0)):
+        if x2 is not None and self.segments is None and (x.shape[-1] % 64 != 0 or x2.shape[-1] % 64 != 0):
             # channel counts of concatenated sources: each is padded to 64 separately, so the layout only differs from the
             # load-time pack (and a repack is only needed) when one of them is not a multiple of 64 — never on this path
-            self.segments = [x.shape[-1], x2.shape[-1]]
-            self._pk_key = None
+            self.segments = (x.shape[-1], x2.shape[-1])
         w, b = self.packed()
         if pad is None:
             pad = (self.padding, self.padding)

@@ -119,8 +119,8 @@ class _PatchEmbed(H._Packed):
         self.patch_size = tuple(patch_size)
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=self.patch_size, stride=self.patch_size)   # parameter holder
 
-    def _key(self):
-        return tuple((p.data_ptr(), p._version, str(p.device)) for p in self.proj.parameters())
+    def _sources(self):
+        return self.proj.weight, self.proj.bias
 
     def _pack(self):
         w = self.proj.weight
