@@ -471,6 +471,18 @@ int udt_local_loss_bwd(const float* probs, const float* mask, const float* seg_m
                        float* loss_accum, float* scratch /* n_samples * seg_l * 2 floats: the tokens' scores */, int32_t n_samples,
                        int32_t mask_batch, int32_t heads, int32_t size, int32_t L, int32_t seg_l, int32_t Hm, int32_t Wm, float weight,
                        void* stream);
+/* the same on h x w maps (n = h * w tokens in row-major order, token = y * w + x; h * w <= 120 * 120; the mask is resized per axis,
+ * nearest: src = floor(dst * in / out)).  udt_local_loss_bwd is this with h = w = size. */
+int udt_local_loss_bwd_hw(const float* probs, const float* mask, const float* seg_mask, const float* gkernel9, float* d_probs,
+                          float* loss_accum, float* scratch /* n_samples * seg_l * 2 floats */, int32_t n_samples, int32_t mask_batch,
+                          int32_t heads, int32_t h, int32_t w, int32_t L, int32_t seg_l, int32_t Hm, int32_t Wm, float weight,
+                          void* stream);
+/* udt_local_loss_tiled's score on h x w maps, cut like udt_local_loss_bwd_hw (the same kernels, no gradient): one workgroup per
+ * (context token, sample), then one per sample; loss_accum fp32 [n_samples] += the term.  Bit-equal to udt_local_loss_tiled
+ * for h == w. */
+int udt_local_loss_tiled_hw(const float* probs, const float* mask, const float* seg_mask, const float* gkernel9, float* loss_accum,
+                            float* scratch /* n_samples * seg_l * 2 floats */, int32_t n_samples, int32_t mask_batch, int32_t heads,
+                            int32_t h, int32_t w, int32_t L, int32_t seg_l, int32_t Hm, int32_t Wm, void* stream);
 /* LayerNorm backward-data (nn.LayerNorm of attention.py:310-339): x, dy bf16 [rows, C] -> dx bf16 (+ add bf16 [rows, C] if given:
  * the gradient that arrives over the residual connection); statistics recomputed from x; C % 8 == 0, C <= 2048 */
 int udt_layernorm_bwd(const void* x, const void* dy, const float* gamma, const void* add, void* dx, int64_t rows, int32_t C, float eps,
@@ -525,6 +537,11 @@ int udt_xattn_bwd_kv(const void* q, const void* v, const float* probs, const flo
 int udt_local_loss_seg_bwd(const float* probs, const float* seg, const float* seg_mask, const float* gkernel9, float* d_probs,
                            float* loss_accum, float* scratch /* B * seg_l floats: the tokens' terms */, int32_t B, int32_t heads,
                            int32_t size, int32_t L, int32_t seg_l, int32_t Hs, int32_t Ws, float weight, void* stream);
+/* the same on h x w maps (row-major tokens, h * w <= 120 * 120; seg resized per axis, nearest); udt_local_loss_seg_bwd is this with
+ * h = w = size */
+int udt_local_loss_seg_bwd_hw(const float* probs, const float* seg, const float* seg_mask, const float* gkernel9, float* d_probs,
+                              float* loss_accum, float* scratch /* B * seg_l floats */, int32_t B, int32_t heads, int32_t h, int32_t w,
+                              int32_t L, int32_t seg_l, int32_t Hs, int32_t Ws, float weight, void* stream);
 /* eps-prediction loss (loss.py:60-71,131-150; EpsScaling / EpsWeighting): loss fp32 [B] = mean(sigma^-2 (eps * -sigma + noised -
  * target)^2) and d_eps bf16 NHWC [B, hw, cpad] = d mean_b(loss_b) / d eps; eps fp32 NHWC [B, hw, ld_eps], noised / target fp32 NCHW */
 int udt_diff_loss_grad(const float* eps, const float* noised, const float* target, const float* sigma, void* d_eps, float* loss, int32_t B,

@@ -1,4 +1,5 @@
-"""Per-launch trace of ONE UNet sampler step at BASELINE config #2 (8 samples), aggregated by shape."""
+"""Per-launch trace of ONE UNet sampler step at BASELINE config #2 (8 samples), aggregated by shape.
+B=<images> SIZE=<square image size>, or H=<height> W=<width> for a rectangular image (multiples of 64)."""
 import collections, os, re, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -8,13 +9,14 @@ from udifftext_amd import config as C, lib as L, ops, pipeline, synth
 dev = torch.device("cuda", 0)
 torch.set_grad_enabled(False)
 B, size = int(os.environ.get("B", 4)), int(os.environ.get("SIZE", 512))
+HH, WW = int(os.environ.get("H", size)), int(os.environ.get("W", size))
 model = pipeline.build_engine(dev)
 sampler = pipeline.init_sampling(50, 5.0, dev)
-batch, buc = pipeline.prepare_batch(synth.synthetic_batch(B, size, size, 9, seed=1), dev)
+batch, buc = pipeline.prepare_batch(synth.synthetic_batch(B, HH, WW, 9, seed=1), dev)
 c, uc = model.conditioner.get_unconditional_conditioning(batch, batch_uc=buc, force_uc_zero_embeddings=["label"])
 from sgm.modules.diffusionmodules.sampling import _Stepper
-st = _Stepper(model, c, uc, B, (size // 8, size // 8), 5.0)
-x = torch.randn((B, 4, size // 8, size // 8), device=dev) * 14
+st = _Stepper(model, c, uc, B, (HH // 8, WW // 8), 5.0)
+x = torch.randn((B, 4, HH // 8, WW // 8), device=dev) * 14
 sig = sampler._host_sigmas()
 for i in range(3):
     st.step(x, sig[i], sig[i + 1])

@@ -101,14 +101,16 @@ def resblock_fwd(rb, x: torch.Tensor, emb_rows: torch.Tensor, x2: Optional[torch
     return out, bwd
 
 
-def transformer_block_fwd(blk, t1: torch.Tensor, B: int, kv: torch.Tensor, rec: list, name: str, kv_c: Optional[torch.Tensor] = None):
+def transformer_block_fwd(blk, t1: torch.Tensor, B: int, kv: torch.Tensor, rec: list, name: str, kv_c: Optional[torch.Tensor] = None,
+                          hw: Optional[tuple] = None):
     """BasicTransformerBlock (reference attention.py:286-339) on bf16 rows t1 [B * N, C]; kv: the hoisted context projection
     [B, L, 2 C]; kv_c: the projection of the CENTRED context (ops.center_tokens) — its k half replaces kv's in the forward (the
     softmax over the tokens does not see a common shift of the keys) and both halves serve the reverse pass (nor does dS see a common
     shift of the values), see csrc/backward.hip center_tokens_kernel; the t_attn probabilities go to ``rec`` (a dict per map; its
-    ``d_probs`` is filled in before the reverse pass)"""
+    ``d_probs`` is filled in before the reverse pass); hw: (h, w) of the N = h * w tokens of a sample (row-major)"""
     M, Cc = t1.shape
     N = M // B
+    from sgm.modules.attention import map_hw
     a1, ta, ff = blk.attn1, blk.t_attn, blk.ff
     heads = a1.heads
     scale = a1.dim_head ** -0.5
@@ -126,7 +128,7 @@ def transformer_block_fwd(blk, t1: torch.Tensor, B: int, kv: torch.Tensor, rec: 
     # ``pgrads``: set to a dict before the reverse pass to ALSO collect the gradients of this block's trainable parameters (the
     # reference trains t_attn / t_norm only, configs/train/textdesign_sd_2.yaml:4-6), keyed by their state-dict names below ``name``;
     # ``ctx`` / ``ctx_c``: the context rows [B * L, Dc] (plain / centred) behind kv, needed for d to_k / d to_v
-    item = {"name": name, "heads": ta.heads, "size": int(N ** 0.5), "attn_map": probs, "d_probs": None, "pgrads": None,
+    item = {"name": name, "heads": ta.heads, "size": int(N ** 0.5), "hw": map_hw(N, hw), "attn_map": probs, "d_probs": None, "pgrads": None,
             "ctx": None, "ctx_c": None, "block": blk}
     rec.append(item)
     t3 = ta.to_out[0](o2.reshape(M, Cc), residual=t2)
@@ -193,7 +195,7 @@ def spatial_transformer_fwd(st, x: torch.Tensor, kv_list: list, rec: list, name:
     bwds = []
     for i, blk in enumerate(st.transformer_blocks):
         t, b = transformer_block_fwd(blk, t, B, kv_list[i], rec, f"{name}transformer_blocks.{i}.t_attn",
-                                     kv_c=(kv_c_list[i] if kv_c_list is not None else None))
+                                     kv_c=(kv_c_list[i] if kv_c_list is not None else None), hw=(Hh, Ww))
         bwds.append(b)
     out = st.proj_out(t, residual=x.reshape(M, Cc)).reshape(B, Hh, Ww, Cc)
 
@@ -341,7 +343,7 @@ class UNetTape:
 def unet_maps_vjp(unet, x: torch.Tensor, timesteps: torch.Tensor, concat: torch.Tensor, t_context: torch.Tensor,
                   maps_grad) -> torch.Tensor:
     """d F / d x (fp32 [B, 4, h, w]) for a scalar F of the UNet's t_attn probability maps: the tape-mode forward of
-    UNet(cat(x, concat)) records every map as a dict (name, heads, size, attn_map fp32 [B * heads, n, L], d_probs None);
+    UNet(cat(x, concat)) records every map as a dict (name, heads, size, hw, attn_map fp32 [B * heads, n, L], d_probs None);
     ``maps_grad(maps)`` sets ``d_probs`` = d F / d attn_map on the maps F reads (None elsewhere: those layers, and everything
     downstream of the last one read, are not differentiated); then the reverse pass runs."""
     from sgm.modules.diffusionmodules.openaimodel import CPAD
@@ -357,7 +359,7 @@ def unet_maps_vjp(unet, x: torch.Tensor, timesteps: torch.Tensor, concat: torch.
 def unet_local_loss_grad(unet, loss_fn, x: torch.Tensor, timesteps: torch.Tensor, concat: torch.Tensor, t_context: torch.Tensor,
                          mask: torch.Tensor, seg_mask: torch.Tensor):
     """(local_loss fp32 [B], d sum(local_loss) / d x fp32 [B, 4, h, w]) for x fp32 NCHW: the UNet sees cat(x, concat) and the
-    t_attn maps of size >= loss_fn.min_attn_size are scored by get_min_local_loss (reference sampling.py:233-252, loss.py:192-235)"""
+    t_attn maps that loss_fn.scores_map(hw) selects are scored by get_min_local_loss (reference sampling.py:233-252, loss.py:192-235)"""
     B = x.shape[0]
     maskf, seg = mask.float().contiguous(), seg_mask.float().contiguous()
     gk = loss_fn.g_kernel[0, 0].reshape(9).float().contiguous()
@@ -365,12 +367,12 @@ def unet_local_loss_grad(unet, loss_fn, x: torch.Tensor, timesteps: torch.Tensor
     count = [0]
 
     def maps_grad(rec):
-        used = [it for it in rec if it["size"] >= loss_fn.min_attn_size]
+        used = [it for it in rec if loss_fn.scores_map(it["hw"])]
         if not used:
             raise ValueError("no t_attn map reaches loss_fn.min_attn_size: the local loss is undefined for this latent size")
         for it in used:
             it["d_probs"] = torch.zeros_like(it["attn_map"])
-            ops.local_loss_bwd(it["attn_map"], maskf, seg, gk, it["d_probs"], loss, it["heads"], it["size"], 1.0 / len(used))
+            ops.local_loss_bwd_hw(it["attn_map"], maskf, seg, gk, it["d_probs"], loss, it["heads"], it["hw"], 1.0 / len(used))
         count[0] = len(used)
     grad = unet_maps_vjp(unet, x, timesteps, concat, t_context, maps_grad)
     return loss / count[0], grad

@@ -373,6 +373,8 @@ __global__ void __launch_bounds__(256) xattn_bwd_kernel(const XattnBwdParams p) 
 // torch.max / torch.min do on the CPU.  d_probs must be zero-initialised by the caller (other contributions may be accumulated into
 // it afterwards).  (One workgroup per sample looping over the tokens: 184 us per call at 64 x 64 — a batch-1 attend-and-excite
 // evaluation makes fifteen.)  scratch: fp32 [n_samples][seg_l][2] = (masked maximum, its pixel index as int bits).
+// Maps are h x w, tokens row-major (n = y * w + x); the three helpers below carry that indexing for the forward score
+// (udt_local_loss_tiled_hw: the same two kernels with d_probs == NULL), this backward and the training step's seg form.
 UDT_DEVINL void ll_head_mean(const float* __restrict__ probs, float* amap, int b, int l, int heads, int n, int L) {
   for (int i = threadIdx.x; i < n; i += 256) {
     float a = 0.f;
@@ -381,14 +383,14 @@ UDT_DEVINL void ll_head_mean(const float* __restrict__ probs, float* amap, int b
   }
 }
 
-UDT_DEVINL float ll_blur(const float* amap, const float* __restrict__ gk, int y, int x, int size) {
+UDT_DEVINL float ll_blur(const float* amap, const float* __restrict__ gk, int y, int x, int h, int w) {
   float acc = 0.f;
 #pragma unroll
   for (int dy = -1; dy <= 1; ++dy)
 #pragma unroll
     for (int dx = -1; dx <= 1; ++dx) {
       const int yy = y + dy, xx = x + dx;
-      if (yy >= 0 && yy < size && xx >= 0 && xx < size) acc += gk[(dy + 1) * 3 + dx + 1] * amap[yy * size + xx];
+      if (yy >= 0 && yy < h && xx >= 0 && xx < w) acc += gk[(dy + 1) * 3 + dx + 1] * amap[yy * w + xx];
     }
   return acc;
 }
@@ -404,20 +406,21 @@ UDT_DEVINL void ll_wave_argmax(float& mx, int& mi) {
 
 __global__ void __launch_bounds__(256) local_loss_token_kernel(const float* __restrict__ probs, const float* __restrict__ mask,
                                                                const float* __restrict__ gk, float* __restrict__ scratch, int heads,
-                                                               int size, int L, int seg_l, int Hm, int Wm, int mask_batch) {
+                                                               int h, int w, int L, int seg_l, int Hm, int Wm, int mask_batch) {
   extern __shared__ __attribute__((aligned(16))) float lbsm[];
-  float* amap = lbsm;                         // [size * size]
-  float* redv = lbsm + size * size;           // [4] wave maxima
+  float* amap = lbsm;                         // [h * w], row-major: token i = y * w + x
+  float* redv = lbsm + h * w;                 // [4] wave maxima
   int* redi = reinterpret_cast<int*>(redv + 4);   // [4] their pixel indices
-  const int l = blockIdx.x, b = blockIdx.y, bm = b % mask_batch, t = threadIdx.x, n = size * size;
+  const int l = blockIdx.x, b = blockIdx.y, bm = b % mask_batch, t = threadIdx.x, n = h * w;
   ll_head_mean(probs, amap, b, l, heads, n, L);
   __syncthreads();
   float mx = -INFINITY;
   int mi = 0x7fffffff;
   for (int i = t; i < n; i += 256) {
-    const int y = i / size, x = i - y * size;
-    const float acc = ll_blur(amap, gk, y, x, size);
-    const int my = (int)(((long long)y * Hm) / size), mxx = (int)(((long long)x * Wm) / size);
+    const int y = i / w, x = i - y * w;
+    const float acc = ll_blur(amap, gk, y, x, h, w);
+    // F.interpolate(mask, (h, w)) nearest, per axis: src = floor(dst * in / out)
+    const int my = (int)(((long long)y * Hm) / h), mxx = (int)(((long long)x * Wm) / w);
     const float val = mask[((long long)bm * Hm + my) * Wm + mxx] * acc;
     if (val > mx) { mx = val; mi = i; }      // (i ascends per thread: the first maximum of the thread's pixels)
   }
@@ -427,8 +430,8 @@ __global__ void __launch_bounds__(256) local_loss_token_kernel(const float* __re
   if (t == 0) {
     float m4 = redv[0];
     int i4 = redi[0];
-    for (int w = 1; w < 4; ++w)
-      if (redv[w] > m4 || (redv[w] == m4 && redi[w] < i4)) { m4 = redv[w]; i4 = redi[w]; }
+    for (int k = 1; k < 4; ++k)
+      if (redv[k] > m4 || (redv[k] == m4 && redi[k] < i4)) { m4 = redv[k]; i4 = redi[k]; }
     float* dst = scratch + ((long long)b * seg_l + l) * 2;
     dst[0] = m4;
     reinterpret_cast<int*>(dst)[1] = i4 == 0x7fffffff ? 0 : i4;
@@ -437,9 +440,9 @@ __global__ void __launch_bounds__(256) local_loss_token_kernel(const float* __re
 
 __global__ void __launch_bounds__(256) local_loss_finish_kernel(const float* __restrict__ scratch, const float* __restrict__ mask,
                                                                 const float* __restrict__ seg, const float* __restrict__ gk,
-                                                                float* __restrict__ d_probs, float* __restrict__ loss, int heads, int size,
-                                                                int L, int seg_l, int Hm, int Wm, int mask_batch, float weight) {
-  const int b = blockIdx.x, bm = b % mask_batch, t = threadIdx.x, n = size * size;
+                                                                float* __restrict__ d_probs, float* __restrict__ loss, int heads, int h,
+                                                                int w, int L, int seg_l, int Hm, int Wm, int mask_batch, float weight) {
+  const int b = blockIdx.x, bm = b % mask_batch, t = threadIdx.x, n = h * w;
   float best = INFINITY;                       // (every thread walks the <= 16 tokens the same way)
   int ls = 0, ns = 0;
   for (int l = 0; l < seg_l; ++l) {
@@ -448,14 +451,15 @@ __global__ void __launch_bounds__(256) local_loss_finish_kernel(const float* __r
     if (pl < best) { best = pl; ls = l; ns = reinterpret_cast<const int*>(src)[1]; }
   }
   if (t == 0 && loss) loss[b] += -best;
-  const int ys = ns / size, xs = ns - ys * size;
-  const int my = (int)(((long long)ys * Hm) / size), mxx = (int)(((long long)xs * Wm) / size);
+  if (!d_probs) return;                        // (the forward score: udt_local_loss_tiled_hw)
+  const int ys = ns / w, xs = ns - ys * w;
+  const int my = (int)(((long long)ys * Hm) / h), mxx = (int)(((long long)xs * Wm) / w);
   const float coef = -weight * mask[((long long)bm * Hm + my) * Wm + mxx] / (float)heads;
   for (int i = t; i < 9 * heads; i += 256) {
     const int hh = i / 9, tap = i - hh * 9;
     const int yy = ys + tap / 3 - 1, xx = xs + tap % 3 - 1;
-    if (yy >= 0 && yy < size && xx >= 0 && xx < size)
-      d_probs[(((long long)b * heads + hh) * n + yy * size + xx) * L + ls] += coef * gk[tap];
+    if (yy >= 0 && yy < h && xx >= 0 && xx < w)
+      d_probs[(((long long)b * heads + hh) * n + yy * w + xx) * L + ls] += coef * gk[tap];
   }
 }
 
@@ -1262,12 +1266,12 @@ __global__ void __launch_bounds__(256) xattn_bwd_kv_reduce_kernel(const float* _
 __global__ void __launch_bounds__(256) local_loss_seg_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ segmap,
                                                                  const float* __restrict__ segm, const float* __restrict__ gk,
                                                                  float* __restrict__ d_probs, float* __restrict__ scratch, int heads,
-                                                                 int size, int L, int seg_l, int Hs, int Ws, float weight) {
+                                                                 int h, int w, int L, int seg_l, int Hs, int Ws, float weight) {
   extern __shared__ __attribute__((aligned(16))) float lssm[];
   float* amap = lssm;
-  float* redv = lssm + size * size;            // [8] wave maxima (inside 0..3, outside 4..7)
+  float* redv = lssm + h * w;                  // [8] wave maxima (inside 0..3, outside 4..7)
   int* redi = reinterpret_cast<int*>(redv + 8);   // [8]
-  const int l = blockIdx.x, b = blockIdx.y, t = threadIdx.x, n = size * size;
+  const int l = blockIdx.x, b = blockIdx.y, t = threadIdx.x, n = h * w;
   const float sm = segm[(long long)b * seg_l + l];
   if (sm == 0.f) {                                             // (uniform over the workgroup)
     if (t == 0) scratch[(long long)b * seg_l + l] = 0.f;
@@ -1280,9 +1284,9 @@ __global__ void __launch_bounds__(256) local_loss_seg_bwd_kernel(const float* __
   float mp = -INFINITY, mn = -INFINITY;
   int ip = 0x7fffffff, in_ = 0x7fffffff;
   for (int i = t; i < n; i += 256) {
-    const int y = i / size, x = i - y * size;
-    const float acc = ll_blur(amap, gk, y, x, size);
-    const int sy = (int)(((long long)y * Hs) / size), sx = (int)(((long long)x * Ws) / size);
+    const int y = i / w, x = i - y * w;
+    const float acc = ll_blur(amap, gk, y, x, h, w);
+    const int sy = (int)(((long long)y * Hs) / h), sx = (int)(((long long)x * Ws) / w);
     const float sv = segmap[(((long long)b * seg_l + l) * Hs + sy) * Ws + sx];
     const float vp = sv * acc, vn = (1.0f - sv) * acc;
     if (vp > mp) { mp = vp; ip = i; }
@@ -1292,9 +1296,9 @@ __global__ void __launch_bounds__(256) local_loss_seg_bwd_kernel(const float* __
   ll_wave_argmax(mn, in_);
   if ((t & 63) == 0) { redv[t >> 6] = mp; redi[t >> 6] = ip; redv[4 + (t >> 6)] = mn; redi[4 + (t >> 6)] = in_; }
   __syncthreads();
-  for (int w = 0; w < 4; ++w) {                              // (every thread combines the four waves the same way)
-    if (redv[w] > mp || (redv[w] == mp && redi[w] < ip)) { mp = redv[w]; ip = redi[w]; }
-    if (redv[4 + w] > mn || (redv[4 + w] == mn && redi[4 + w] < in_)) { mn = redv[4 + w]; in_ = redi[4 + w]; }
+  for (int k = 0; k < 4; ++k) {                              // (every thread combines the four waves the same way)
+    if (redv[k] > mp || (redv[k] == mp && redi[k] < ip)) { mp = redv[k]; ip = redi[k]; }
+    if (redv[4 + k] > mn || (redv[4 + k] == mn && redi[4 + k] < in_)) { mn = redv[4 + k]; in_ = redi[4 + k]; }
   }
   if (t == 0) scratch[(long long)b * seg_l + l] = sm * (mn - mp);
   const float cbase = weight * sm / ssum / (float)heads;
@@ -1303,13 +1307,13 @@ __global__ void __launch_bounds__(256) local_loss_seg_bwd_kernel(const float* __
     const int which = k / 9, tap = k - which * 9;             // 0: inside (p, minus sign), 1: outside (n, plus sign)
     const int ns = which ? in_ : ip;
     if (ns == 0x7fffffff) continue;
-    const int ys = ns / size, xs = ns - ys * size;
-    const int sy = (int)(((long long)ys * Hs) / size), sx = (int)(((long long)xs * Ws) / size);
+    const int ys = ns / w, xs = ns - ys * w;
+    const int sy = (int)(((long long)ys * Hs) / h), sx = (int)(((long long)xs * Ws) / w);
     const float sv = segmap[(((long long)b * seg_l + l) * Hs + sy) * Ws + sx];
     const float coef = which ? cbase * (1.0f - sv) : -cbase * sv;
     const int yy = ys + tap / 3 - 1, xx = xs + tap % 3 - 1;
-    if (yy >= 0 && yy < size && xx >= 0 && xx < size)
-      atomicAdd(&d_probs[(((long long)b * heads + hh) * n + yy * size + xx) * L + l], coef * gk[tap]);
+    if (yy >= 0 && yy < h && xx >= 0 && xx < w)
+      atomicAdd(&d_probs[(((long long)b * heads + hh) * n + yy * w + xx) * L + l], coef * gk[tap]);
   }
 }
 
@@ -1433,21 +1437,47 @@ extern "C" int udt_xattn_bwd(const void* k, const void* v, const float* probs, c
   return UDT_OK;
 }
 
-extern "C" int udt_local_loss_bwd(const float* probs, const float* mask, const float* seg_mask, const float* gkernel9, float* d_probs,
-                                  float* loss_accum, float* scratch, int32_t n_samples, int32_t mask_batch, int32_t heads, int32_t size,
-                                  int32_t L, int32_t seg_l, int32_t Hm, int32_t Wm, float weight, void* stream) {
-  if (!probs || !mask || !seg_mask || !gkernel9 || !d_probs || !scratch) return UDT_ERR_BAD_ARG;
-  if (n_samples <= 0 || mask_batch <= 0 || n_samples % mask_batch != 0 || heads <= 0 || size <= 0 || size > 120 || L <= 0 ||
-      seg_l <= 0 || seg_l > L) return UDT_ERR_BAD_SHAPE;
+// Token kernel + finish; d_probs NULL: the forward score alone.  The map of one token lives in LDS: h * w <= 120 * 120 floats (+ 64 B)
+// fit the default 64 KiB dynamic-LDS limit.
+static int local_loss_hw_impl(const float* probs, const float* mask, const float* seg_mask, const float* gkernel9, float* d_probs,
+                              float* loss_accum, float* scratch, int32_t n_samples, int32_t mask_batch, int32_t heads, int32_t h, int32_t w,
+                              int32_t L, int32_t seg_l, int32_t Hm, int32_t Wm, float weight, void* stream) {
+  if (!probs || !mask || !seg_mask || !gkernel9 || !scratch) return UDT_ERR_BAD_ARG;
+  if (n_samples <= 0 || mask_batch <= 0 || n_samples % mask_batch != 0 || heads <= 0 || h <= 0 || w <= 0 ||
+      (long long)h * w > 120 * 120 || L <= 0 || seg_l <= 0 || seg_l > L || Hm <= 0 || Wm <= 0) return UDT_ERR_BAD_SHAPE;
   UDT_BWD_STREAM;
-  const size_t smem = ((size_t)size * size + 16) * sizeof(float);
-  hipLaunchKernelGGL(local_loss_token_kernel, dim3(seg_l, n_samples), dim3(256), smem, s, probs, mask, gkernel9, scratch, heads, size, L,
+  const size_t smem = ((size_t)h * w + 16) * sizeof(float);
+  hipLaunchKernelGGL(local_loss_token_kernel, dim3(seg_l, n_samples), dim3(256), smem, s, probs, mask, gkernel9, scratch, heads, h, w, L,
                      seg_l, Hm, Wm, mask_batch);
   UDT_CHECK_LAUNCH();
   hipLaunchKernelGGL(local_loss_finish_kernel, dim3(n_samples), dim3(256), 0, s, scratch, mask, seg_mask, gkernel9, d_probs, loss_accum,
-                     heads, size, L, seg_l, Hm, Wm, mask_batch, weight);
+                     heads, h, w, L, seg_l, Hm, Wm, mask_batch, weight);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
+}
+
+extern "C" int udt_local_loss_bwd_hw(const float* probs, const float* mask, const float* seg_mask, const float* gkernel9, float* d_probs,
+                                     float* loss_accum, float* scratch, int32_t n_samples, int32_t mask_batch, int32_t heads, int32_t h,
+                                     int32_t w, int32_t L, int32_t seg_l, int32_t Hm, int32_t Wm, float weight, void* stream) {
+  if (!d_probs) return UDT_ERR_BAD_ARG;
+  return local_loss_hw_impl(probs, mask, seg_mask, gkernel9, d_probs, loss_accum, scratch, n_samples, mask_batch, heads, h, w, L, seg_l, Hm,
+                            Wm, weight, stream);
+}
+
+extern "C" int udt_local_loss_bwd(const float* probs, const float* mask, const float* seg_mask, const float* gkernel9, float* d_probs,
+                                  float* loss_accum, float* scratch, int32_t n_samples, int32_t mask_batch, int32_t heads, int32_t size,
+                                  int32_t L, int32_t seg_l, int32_t Hm, int32_t Wm, float weight, void* stream) {
+  if (size > 120) return UDT_ERR_BAD_SHAPE;
+  return udt_local_loss_bwd_hw(probs, mask, seg_mask, gkernel9, d_probs, loss_accum, scratch, n_samples, mask_batch, heads, size, size, L,
+                               seg_l, Hm, Wm, weight, stream);
+}
+
+extern "C" int udt_local_loss_tiled_hw(const float* probs, const float* mask, const float* seg_mask, const float* gkernel9,
+                                       float* loss_accum, float* scratch, int32_t n_samples, int32_t mask_batch, int32_t heads, int32_t h,
+                                       int32_t w, int32_t L, int32_t seg_l, int32_t Hm, int32_t Wm, void* stream) {
+  if (!loss_accum) return UDT_ERR_BAD_ARG;
+  return local_loss_hw_impl(probs, mask, seg_mask, gkernel9, nullptr, loss_accum, scratch, n_samples, mask_batch, heads, h, w, L, seg_l, Hm,
+                            Wm, 0.f, stream);
 }
 
 extern "C" int udt_layernorm_bwd(const void* x, const void* dy, const float* gamma, const void* add, void* dx, int64_t rows, int32_t C,
@@ -1677,21 +1707,30 @@ extern "C" int udt_xattn_bwd_kv(const void* q, const void* v, const float* probs
   return UDT_OK;
 }
 
-extern "C" int udt_local_loss_seg_bwd(const float* probs, const float* seg, const float* seg_mask, const float* gkernel9, float* d_probs,
-                                      float* loss_accum, float* scratch, int32_t B, int32_t heads, int32_t size, int32_t L, int32_t seg_l,
-                                      int32_t Hs, int32_t Ws, float weight, void* stream) {
+extern "C" int udt_local_loss_seg_bwd_hw(const float* probs, const float* seg, const float* seg_mask, const float* gkernel9, float* d_probs,
+                                         float* loss_accum, float* scratch, int32_t B, int32_t heads, int32_t h, int32_t w, int32_t L,
+                                         int32_t seg_l, int32_t Hs, int32_t Ws, float weight, void* stream) {
   if (!probs || !seg || !seg_mask || !gkernel9 || !d_probs || !scratch) return UDT_ERR_BAD_ARG;
-  if (B <= 0 || heads <= 0 || size <= 0 || size > 120 || L <= 0 || seg_l <= 0 || seg_l > L) return UDT_ERR_BAD_SHAPE;
+  if (B <= 0 || heads <= 0 || h <= 0 || w <= 0 || (long long)h * w > 120 * 120 || L <= 0 || seg_l <= 0 || seg_l > L || Hs <= 0 ||
+      Ws <= 0) return UDT_ERR_BAD_SHAPE;
   UDT_BWD_STREAM;
-  const size_t smem = ((size_t)size * size + 32) * sizeof(float);
+  const size_t smem = ((size_t)h * w + 32) * sizeof(float);
   hipLaunchKernelGGL(local_loss_seg_bwd_kernel, dim3(seg_l, B), dim3(256), smem, s, probs, seg, seg_mask, gkernel9, d_probs, scratch, heads,
-                     size, L, seg_l, Hs, Ws, weight);
+                     h, w, L, seg_l, Hs, Ws, weight);
   UDT_CHECK_LAUNCH();
   if (loss_accum) {
     hipLaunchKernelGGL(local_loss_seg_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, scratch, seg_mask, loss_accum, B, seg_l);
     UDT_CHECK_LAUNCH();
   }
   return UDT_OK;
+}
+
+extern "C" int udt_local_loss_seg_bwd(const float* probs, const float* seg, const float* seg_mask, const float* gkernel9, float* d_probs,
+                                      float* loss_accum, float* scratch, int32_t B, int32_t heads, int32_t size, int32_t L, int32_t seg_l,
+                                      int32_t Hs, int32_t Ws, float weight, void* stream) {
+  if (size > 120) return UDT_ERR_BAD_SHAPE;
+  return udt_local_loss_seg_bwd_hw(probs, seg, seg_mask, gkernel9, d_probs, loss_accum, scratch, B, heads, size, size, L, seg_l, Hs, Ws,
+                                   weight, stream);
 }
 
 extern "C" int udt_diff_loss_grad(const float* eps, const float* noised, const float* target, const float* sigma, void* d_eps, float* loss,

@@ -875,6 +875,29 @@ def local_loss_accumulate(probs: torch.Tensor, mask: torch.Tensor, seg_mask: tor
                                           seg_mask.shape[1], mask.shape[2], mask.shape[3], _stream()), "udt_local_loss_tiled")
 
 
+def _check_map_hw(probs: torch.Tensor, hw, what: str):
+    """(h, w) of a [b * heads, n, L] probability map; n != h * w would be scored on a wrong row pitch: refuse it"""
+    h, w = int(hw[0]), int(hw[1])
+    if probs.dim() != 3 or h <= 0 or w <= 0 or probs.shape[1] != h * w:
+        raise ValueError(f"{what}: maps of shape {tuple(probs.shape)} do not hold h * w = {h} * {w} tokens")
+    return h, w
+
+
+def local_loss_accumulate_hw(probs: torch.Tensor, mask: torch.Tensor, seg_mask: torch.Tensor, gk9: torch.Tensor,
+                             loss: torch.Tensor, heads: int, hw) -> None:
+    """``local_loss_accumulate`` on h x w maps (tokens row-major, n = y * w + x): udt_local_loss_tiled_hw, one workgroup per
+    (context token, sample)"""
+    h, w = _check_map_hw(probs, hw, "local_loss_accumulate_hw")
+    B = mask.shape[0]
+    n = probs.shape[0] // heads
+    Lc = probs.shape[-1]
+    assert probs.is_contiguous() and loss.is_contiguous() and loss.numel() == n and n % B == 0
+    scratch = torch.empty((n, seg_mask.shape[1], 2), dtype=torch.float32, device=probs.device)
+    L.check(L.load().udt_local_loss_tiled_hw(_ptr(probs), _ptr(mask), _ptr(seg_mask), _ptr(gk9), _ptr(loss), _ptr(scratch), n, B, heads,
+                                             h, w, Lc, seg_mask.shape[1], mask.shape[2], mask.shape[3], _stream()),
+            "udt_local_loss_tiled_hw")
+
+
 def add_(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     _bf16(x); _bf16(y)
     assert x.is_contiguous() and y.is_contiguous() and x.numel() == y.numel()
@@ -941,6 +964,21 @@ def local_loss_bwd(probs: torch.Tensor, mask: torch.Tensor, seg_mask: torch.Tens
     L.check(L.load().udt_local_loss_bwd(_ptr(probs), _ptr(mask), _ptr(seg_mask), _ptr(gk9), _ptr(d_probs), _ptr(loss), _ptr(scratch), n, B,
                                         heads, size, Lc, seg_mask.shape[1], mask.shape[2], mask.shape[3], weight, _stream()),
             "udt_local_loss_bwd")
+
+
+def local_loss_bwd_hw(probs: torch.Tensor, mask: torch.Tensor, seg_mask: torch.Tensor, gk9: torch.Tensor, d_probs: torch.Tensor,
+                      loss: Optional[torch.Tensor], heads: int, hw, weight: float) -> None:
+    """``local_loss_bwd`` on h x w maps: udt_local_loss_bwd_hw"""
+    h, w = _check_map_hw(probs, hw, "local_loss_bwd_hw")
+    B = mask.shape[0]
+    n = probs.shape[0] // heads
+    Lc = probs.shape[-1]
+    assert probs.is_contiguous() and d_probs.is_contiguous() and d_probs.shape == probs.shape and n % B == 0
+    assert d_probs.dtype == torch.float32 and (loss is None or (loss.is_contiguous() and loss.numel() == n))
+    scratch = torch.empty((n, seg_mask.shape[1], 2), dtype=torch.float32, device=probs.device)
+    L.check(L.load().udt_local_loss_bwd_hw(_ptr(probs), _ptr(mask), _ptr(seg_mask), _ptr(gk9), _ptr(d_probs), _ptr(loss), _ptr(scratch), n,
+                                           B, heads, h, w, Lc, seg_mask.shape[1], mask.shape[2], mask.shape[3], weight, _stream()),
+            "udt_local_loss_bwd_hw")
 
 
 def layer_norm_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, eps: float = 1e-5,
@@ -1101,6 +1139,19 @@ def local_loss_seg_bwd(probs: torch.Tensor, seg: torch.Tensor, seg_mask: torch.T
     L.check(L.load().udt_local_loss_seg_bwd(_ptr(probs), _ptr(seg), _ptr(seg_mask), _ptr(gk9), _ptr(d_probs), _ptr(loss), _ptr(scratch), B,
                                             heads, size, probs.shape[-1], seg.shape[1], seg.shape[2], seg.shape[3], weight, _stream()),
             "udt_local_loss_seg_bwd")
+
+
+def local_loss_seg_bwd_hw(probs: torch.Tensor, seg: torch.Tensor, seg_mask: torch.Tensor, gk9: torch.Tensor, d_probs: torch.Tensor,
+                          loss: Optional[torch.Tensor], heads: int, hw, weight: float) -> None:
+    """``local_loss_seg_bwd`` on h x w maps: udt_local_loss_seg_bwd_hw"""
+    h, w = _check_map_hw(probs, hw, "local_loss_seg_bwd_hw")
+    B = seg.shape[0]
+    assert probs.is_contiguous() and d_probs.is_contiguous() and d_probs.shape == probs.shape and probs.shape[0] == B * heads
+    assert seg.dtype == torch.float32 and seg.is_contiguous() and seg_mask.is_contiguous() and seg.shape[1] == seg_mask.shape[1]
+    scratch = torch.empty((B, seg.shape[1]), dtype=torch.float32, device=probs.device)
+    L.check(L.load().udt_local_loss_seg_bwd_hw(_ptr(probs), _ptr(seg), _ptr(seg_mask), _ptr(gk9), _ptr(d_probs), _ptr(loss), _ptr(scratch),
+                                               B, heads, h, w, probs.shape[-1], seg.shape[1], seg.shape[2], seg.shape[3], weight,
+                                               _stream()), "udt_local_loss_seg_bwd_hw")
 
 
 def diff_loss_grad(eps: torch.Tensor, noised: torch.Tensor, target: torch.Tensor, sigma: torch.Tensor, cpad: int = 64):

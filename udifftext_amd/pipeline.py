@@ -129,6 +129,13 @@ def _cat_cond(conds):
     return out
 
 
+def _image_hw(batch: dict) -> tuple:
+    """(H, W) of a batch's images, read as parallel.predict_sharded reads it"""
+    if "target_size_as_tuple" in batch:
+        return tuple(int(v) for v in batch["target_size_as_tuple"][0])
+    return tuple(int(v) for v in batch["image"].shape[-2:])
+
+
 _LANE_STREAMS: dict = {}
 
 
@@ -147,14 +154,16 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
     and the VAE decode of a batch are enqueued back to back on its lane's stream; the lanes run free of each other and the
     host only synchronises once, at the end.
     Conditioning and noise draws stay per input batch, in the order and from the CPU generator that calling
-    ``predict`` batch by batch would use; decoding runs on the fused batch.
+    ``predict`` batch by batch would use; decoding runs on the fused batch.  With automatic fusing (``fuse`` 0) only consecutive
+    batches of one image size are joined; an explicit ``fuse`` > 1 over batches of different sizes raises ValueError.
     ``image_seeds[k]`` (optional): one seed per image of batch k — its draws then come from per-image generators
     (``rng.per_image``), independent of batching and sharding.  Returns [(samples, z), ...] in input order."""
     from udifftext_amd import ops
     device = device or next(model.parameters()).device
     n = max(1, int(in_flight if in_flight is not None else IN_FLIGHT))
     f = int(fuse if fuse is not None else FUSE)
-    if f <= 0:
+    auto = f <= 0
+    if auto:
         f = min(4, max(1, -(-len(batches) // n)))
     if cfgs.aae_enabled or cfgs.detailed:
         raise NotImplementedError("attend-and-excite / detailed dumps are out of scope (see EulerEDMSampler.__call__)")
@@ -174,7 +183,17 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
     # had no sampling running, and a slow lane held the others.)
     lane_sampler = getattr(sampler, "sample_lane", None)
     draw_noise = getattr(sampler, "draw_step_noise", None)
-    units = [list(range(i, min(i + f, len(batches)))) for i in range(0, len(batches), f)]
+    if auto:
+        # automatic fusing joins consecutive batches only while their image size is equal (one size per sampling batch, as the
+        # reference's target_size_as_tuple[0]): a list of mixed sizes works; an explicit fuse > 1 over mixed sizes raises below
+        units = []
+        for i, b in enumerate(batches):
+            if units and len(units[-1]) < f and _image_hw(batches[units[-1][0]]) == _image_hw(b):
+                units[-1].append(i)
+            else:
+                units.append([i])
+    else:
+        units = [list(range(i, min(i + f, len(batches)))) for i in range(0, len(batches), f)]
     # lanes in use: as few as keep every lane equally loaded — 4 sampling batches on 3 lanes run as 2 + 2 on TWO lanes (each planned
     # for half of the CUs), not as 2 + 1 + 1 with the 4th batch alone on a lane planned for a third of the chip while two lanes idle
     rounds = -(-len(units) // n) if units else 1

@@ -86,6 +86,18 @@ class FeedForward(nn.Module):
         return self.net[2](h, residual=residual)
 
 
+def map_hw(n_tokens: int, hw=None) -> tuple:
+    """(h, w) of a map of n_tokens = h * w row-major tokens.  The SpatialTransformer hands in the geometry of its NHWC input; a
+    module called on bare token rows (hw None) can only mean a square map — anything else is refused, not guessed."""
+    if hw is None:
+        s = int(n_tokens ** 0.5)
+        hw = (s, s)
+    h, w = int(hw[0]), int(hw[1])
+    if h <= 0 or w <= 0 or h * w != n_tokens:
+        raise ValueError(f"a t_attn map of {n_tokens} tokens is not {h} x {w}: pass hw=(h, w)")
+    return h, w
+
+
 class CrossAttention(H._Packed):
     """text cross-attention over L <= 16 context tokens"""
 
@@ -115,8 +127,8 @@ class CrossAttention(H._Packed):
         B, Lc, Dc = context_bf16.shape
         return ops.linear(context_bf16.reshape(B * Lc, Dc), self.packed()).reshape(B, Lc, -1)
 
-    def forward(self, x, context=None, kv=None, residual=None, emit_map: bool = False, out=None):
-        """x: bf16 [B, N, C]"""
+    def forward(self, x, context=None, kv=None, residual=None, emit_map: bool = False, out=None, hw=None):
+        """x: bf16 [B, N, C]; hw: (h, w) of the N = h * w tokens (row-major), recorded with an emitted map"""
         inner = self.heads * self.dim_head
         B, N, _ = x.shape
         q = self.to_q(x.reshape(B * N, -1)).reshape(B, N, inner)
@@ -125,7 +137,8 @@ class CrossAttention(H._Packed):
         probs = None
         if emit_map and self.attn_map_cache is not None:
             probs = torch.empty((B * self.heads, N, kv.shape[1]), dtype=torch.float32, device=q.device)
-            self.attn_map_cache["size"] = int(N ** 0.5)
+            self.attn_map_cache["size"] = int(N ** 0.5)            # (the reference's key; meaningless for h != w)
+            self.attn_map_cache["hw"] = map_hw(N, hw)
             self.attn_map_cache["attn_map"] = probs
         o = ops.xattention(q, kv[..., :inner], kv[..., inner:], self.heads, self.dim_head, self.scale, probs=probs)
         res = residual.reshape(B * N, -1) if residual is not None else None
@@ -252,7 +265,7 @@ class BasicTransformerBlock(nn.Module):
                 and n_tokens % (32 if C >= 640 else 64) == 0)       # (the kernel's token tile: csrc/tattn.hip tattn_tt)
 
     def forward(self, x, t_context=None, v_context=None, t_kv=None, emit_map: bool = False, zero_ctx_rows: int = 0,
-                t_fused=None, x8=None, emit_rowstats: bool = False, defer_ff_out: bool = False):
+                t_fused=None, x8=None, emit_rowstats: bool = False, defer_ff_out: bool = False, hw=None):
         """zero_ctx_rows: the first n samples of the batch attend to an all-zero text context (the unconditional
         half of a CFG pair under force_uc_zero_embeddings) — their t_attn branch is x + to_out.bias, no GEMMs.
         t_fused: the block's folded context tables (ops.TattnTables for the samples of x) -> one fused launch.
@@ -275,7 +288,7 @@ class BasicTransformerBlock(nn.Module):
                     self.t_attn(self.t_norm(xc), kv=t_kv[n0:], residual=xc, out=y[n0:])
                 x = y
             else:
-                x = self.t_attn(self.t_norm(x), context=t_context, kv=t_kv, residual=x, emit_map=emit_map)
+                x = self.t_attn(self.t_norm(x), context=t_context, kv=t_kv, residual=x, emit_map=emit_map, hw=hw)
         B, N, C = x.shape
         x2 = x.reshape(B * N, C)
         if fold:
@@ -337,7 +350,8 @@ class SpatialTransformer(nn.Module):
         for i, blk in enumerate(self.transformer_blocks):
             t = blk(t, t_context=t_context, t_kv=(t_kv[i] if t_kv is not None else None), emit_map=emit_map,
                     zero_ctx_rows=zero_ctx_rows, t_fused=(t_fused[i] if t_fused is not None else None),
-                    x8=ops.mx8_of(t) if mx else None, emit_rowstats=(i + 1 < nb), defer_ff_out=(defer and i + 1 == nb))
+                    x8=ops.mx8_of(t) if mx else None, emit_rowstats=(i + 1 < nb), defer_ff_out=(defer and i + 1 == nb),
+                    hw=(Hh, Ww))
         if isinstance(t, tuple):
             hid, t3 = t
             w, b = self.packed_ffproj()

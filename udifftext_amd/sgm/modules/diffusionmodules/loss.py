@@ -49,12 +49,18 @@ class FullLoss(StandardDiffusionLoss):
         g = g / g.sum()
         return g.view(1, 1, kernel_size, kernel_size).tile(out_channels, 1, 1, 1)
 
+    def scores_map(self, hw) -> bool:
+        """a t_attn layer is scored when min(h, w) >= min_attn_size: the reference's ``size >= min_attn_size`` for h == w (it
+        raises for h != w), and never a blur over a map fewer than min_attn_size pixels high or wide"""
+        return min(int(hw[0]), int(hw[1])) >= self.min_attn_size
+
     def get_min_local_loss(self, attn_map_cache, mask, seg_mask, cond_only: bool = False):
         """-> fp32 [n], n = batch of the attention maps (uncond ‖ cond).  mask [B,1,H,W], seg_mask [B, seg_l] with
         n a multiple of B: sample i of the maps is scored against mask[i % B] (for B = 1 this is the reference's
         broadcast; for B > 1 the reference is undefined — SURVEY.md §8a row N — and this is the per-sample rule).
         cond_only: score only the conditional half (the half every caller keeps, reference sampling.py: ``local_loss[B:]``)
-        -> fp32 [n / 2].  One launch per attention map, whatever n is."""
+        -> fp32 [n / 2].  The maps are h x w (``item["hw"]``, tokens row-major), the mask is resized per axis; a layer counts
+        when ``scores_map(hw)``.  Two launches per scored attention map, whatever n is."""
         mask = mask.float().contiguous()
         seg = seg_mask.float().contiguous()
         B = mask.shape[0]
@@ -63,8 +69,8 @@ class FullLoss(StandardDiffusionLoss):
         for item in attn_map_cache:
             if not item["name"].endswith("t_attn") or item["attn_map"] is None:
                 continue
-            heads, size, am = item["heads"], item["size"], item["attn_map"]
-            if size < self.min_attn_size:
+            heads, hw, am = item["heads"], item["hw"], item["attn_map"]
+            if not self.scores_map(hw):
                 continue
             n = am.shape[0] // heads
             assert n % B == 0 and seg.shape[1] <= am.shape[2]
@@ -72,6 +78,6 @@ class FullLoss(StandardDiffusionLoss):
             assert first % B == 0
             if loss is None:
                 loss = torch.zeros((n - first,), dtype=torch.float32, device=am.device)
-            ops.local_loss_accumulate(am[first * heads:], mask, seg, gk, loss, heads, size)
+            ops.local_loss_accumulate_hw(am[first * heads:], mask, seg, gk, loss, heads, hw)
             count += 1
         return loss / count

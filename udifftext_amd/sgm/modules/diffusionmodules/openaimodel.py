@@ -195,7 +195,7 @@ class UnifiedUNetModel(nn.Module):
         self.attn_map_cache = []
         for name, module in self.named_modules():
             if any(name.endswith(t) for t in self.attn_type):
-                item = {"name": name, "heads": module.heads, "size": None, "attn_map": None}
+                item = {"name": name, "heads": module.heads, "size": None, "hw": None, "attn_map": None}
                 self.attn_map_cache.append(item)
                 module.attn_map_cache = item
         self.cache_attn_maps = True          # forward() fills attn_map_cache like the reference; the sampler's
@@ -220,7 +220,7 @@ class UnifiedUNetModel(nn.Module):
         batch; a 3 x 4 grid of the first 12 is written to ``out_dir``/attn_map_<save_name>.png (matplotlib's imshow where the
         reference draws seaborn heatmaps — the returned array is what the sampler passes on to save_segment_map).  Host-side only:
         the maps are whatever the last map-emitting UNet call cached."""
-        maps, heads = [], 1
+        maps, heads, hws = [], 1, set()
         for item in self.attn_map_cache:
             name = item["name"]
             if any(name.startswith(block) for block in self.attn_layers) and name.endswith(attn_type):
@@ -228,13 +228,16 @@ class UnifiedUNetModel(nn.Module):
                     raise RuntimeError(f"save_attn_map: no cached map for {name} — run a map-emitting UNet call first")
                 heads = item["heads"]
                 maps.append(item["attn_map"].detach().float().cpu())
+                hws.add(item["hw"])
         if not maps:
             raise RuntimeError("save_attn_map: save_attn_layers / save_attn_type select no attention layer")
         attn_map = torch.stack(maps, dim=0).mean(dim=0)                     # [b * heads, n, l]
         bh, n, l = attn_map.shape
         attn_map = attn_map.reshape(-1, heads, n, l).mean(dim=1)             # [b, n, l]
         b = attn_map.shape[0]
-        h = w = int(n ** 0.5)
+        if len(hws) != 1:
+            raise RuntimeError(f"save_attn_map: the selected layers have different map sizes {sorted(hws)}")
+        h, w = next(iter(hws))                                               # (the reference's int(n ** 0.5) holds for h == w only)
         attn_map_i = attn_map.permute(0, 2, 1).reshape(b, l, h, w).numpy()[-1]
         try:
             import matplotlib

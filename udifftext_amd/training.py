@@ -39,7 +39,7 @@ def training_loss_and_grads(engine, z: torch.Tensor, cond: dict, seg: torch.Tens
     tape, noised, sigma = training_tape(engine, z, cond, sigma_idx, noise)
     z = z.float().contiguous()
     loss_diff, d_eps = ops.diff_loss_grad(tape.eps, noised, z, sigma)
-    used = [it for it in tape.maps if it["size"] >= loss_fn.min_attn_size]
+    used = [it for it in tape.maps if loss_fn.scores_map(it["hw"])]
     lam = float(loss_fn.lambda_local_loss)
     loss_local = torch.zeros((B,), dtype=torch.float32, device=dev)
     if used:
@@ -47,8 +47,8 @@ def training_loss_and_grads(engine, z: torch.Tensor, cond: dict, seg: torch.Tens
         gk = loss_fn.g_kernel[0, 0].reshape(9).float().contiguous()
         for it in used:
             it["d_probs"] = torch.zeros_like(it["attn_map"])
-            ops.local_loss_seg_bwd(it["attn_map"], segf, segm, gk, it["d_probs"], loss_local, it["heads"], it["size"],
-                                   lam / (len(used) * B))
+            ops.local_loss_seg_bwd_hw(it["attn_map"], segf, segm, gk, it["d_probs"], loss_local, it["heads"], it["hw"],
+                                      lam / (len(used) * B))
     diff = loss_diff.mean()
     local = loss_local.mean() / max(len(used), 1)
     loss_dict = {"loss/diff_loss": diff, "loss/local_loss": local, "loss/full_loss": diff + lam * local}
