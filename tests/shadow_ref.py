@@ -13,7 +13,7 @@ through (PASSTHROUGH); any other ops function without a reference is recorded as
 The reference functions (``ref_*``) are plain torch and device-agnostic: tests/test_shadow_ref_cpu.py pins them on the CPU
 against independent torch compositions.
 
-Bounds, per op class (CLASSES), all taken from the op's existing unit test:
+Bounds, per op class (CLASSES), all taken from the op's existing unit test (the fp32 class's k: from a float32 restatement):
   * per element, scaled to the tensor: |got - ref| <= rtol * |ref| + atol * RMS(ref);
   * localisation: every 32-row x 32-column block of the output has RMS(err) <= k * max(RMS(ref_block), 0.1 * RMS(ref)), so
     one wrong tile fails although the global error is small; k per class, from measurement (see CLASSES).
@@ -40,6 +40,12 @@ F64 = torch.float64
 # bf16-output ops 2.6e-3 (bf16 rounding of the output: 2^-9 rms relative), the e4m3 attention 1.8e-2, the fp32 xattn probabilities
 # 1.6e-7.  conv+gn, gn-table and softmax are not on the shipped path (UDT_FUSE_GN is off; the VAE runs attention_d512): their k
 # is the bf16 one.
+# f32 (posterior_sample, mask_downsample: fp32 in, fp32 out): rtol / atol from tests/test_ops_gpu.py test_layout_and_misc (rtol 1e-5;
+# atol 1e-5 for the posterior sample, 1e-6 for the mask: the class takes the tighter one, scaled by RMS(ref) like every class).  Its k is
+# NOT taken from the kernel: tests/test_shadow_ref_cpu.py test_f32_class_localisation_factor measures the worst 32 x 32 block ratio of a
+# float32 torch restatement of both ops against the float64 references at the shapes the shadow runs produce (moments [4, 64, 64, 8],
+# [1, 32, 48, 8], [2, 32, 48, 8]; masks [4, 1, 512, 512], [2, 1, 256, 384]): 1.16e-7 for the posterior sample (0 for the mask: four binary
+# pixels times 0.25 is exact), times 8 for another operation order and a fast exp -> k = 9.3e-7.  A wrong tile is off by ~1.
 CLASSES = {
     # name             rtol    atol    k
     "gemm":           (1.5e-2, 2e-2, 8e-3),
@@ -55,6 +61,7 @@ CLASSES = {
     "gn-table":       (2e-3, 2e-3, 8e-3),
     "softmax":        (1.5e-2, 1e-3, 8e-3),
     "elementwise":    (1.5e-2, 1e-2, 8e-3),
+    "f32":            (1e-5, 1e-6, 9.3e-7),
     "layout":         (0.0, 0.0, 0.0),
 }
 # rel-RMS bounds of the unit tests that state one (test_mx8_gpu REL_GEMM / REL_ATTN8 / REL_Q8)
@@ -243,6 +250,51 @@ def ref_timestep_embedding(t, dim):
     return torch.cat([torch.cos(a), torch.sin(a)], dim=-1)
 
 
+def ref_masked_attention(q, k, v, heads, scale, mask=None, key_padding_mask=None):
+    """nn.MultiheadAttention's core: per (sample, head) softmax(q k^T * scale + mask, key-padded columns -inf) v.  q [B, Nq, heads*D],
+    k / v [B, Lk, >=heads*D] row views whose first heads*D columns are live; mask [Nq, Lk] additive (may hold -inf),
+    key_padding_mask [B, Lk] (true = ignore) -> fp64 [B, Nq, heads*D]"""
+    B, Nq, Cq = q.shape
+    D = Cq // heads
+    o = torch.empty((B, Nq, heads * D), dtype=F64, device=q.device)
+    for b in range(B):
+        for h in range(heads):
+            sl = slice(h * D, (h + 1) * D)
+            s = (_d(q[b, :, sl]) @ _d(k[b, :, sl]).t()) * scale
+            if mask is not None:
+                s = s + _d(mask)
+            if key_padding_mask is not None:
+                s = s.masked_fill(key_padding_mask[b].bool()[None, :], float("-inf"))
+            o[b, :, sl] = torch.softmax(s, dim=-1) @ _d(v[b, :, sl])
+    return o
+
+
+def ref_posterior_sample(moments, noise, scale):
+    """moments NHWC [B, h, w, ld >= 8] (mean in channels 0..3, logvar in 4..7, whatever ld is), noise NCHW [B, 4, h, w] ->
+    scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise), fp64 NCHW [B, 4, h, w] (the reference's distributions.py clamps)"""
+    m = _d(moments)
+    mean = m[..., 0:4].permute(0, 3, 1, 2)
+    logvar = m[..., 4:8].permute(0, 3, 1, 2).clamp(-30.0, 20.0)
+    return scale * (mean + torch.exp(0.5 * logvar) * _d(noise))
+
+
+def ref_mask_downsample(mask):
+    """the rule udt_mask_downsample implements (csrc/elementwise.hip mask_downsample_kernel): mask [B, 1, H, W] -> [B, 1, H // 8, W // 8],
+    out[oy, ox] = the mean of the four pixels (8 oy + 3 + dy, 8 ox + 3 + dx), dy, dx in {0, 1} — bilinear x 1/8 with
+    align_corners False samples at 8 o + 3.5, halfway between pixels 3 and 4 of each 8 x 8 block, on both axes"""
+    B, _, H, W_ = mask.shape
+    h, w = H // 8, W_ // 8
+    m = _d(mask)[:, :, :8 * h, :8 * w].reshape(B, 1, h, 8, w, 8)
+    return 0.25 * (m[:, :, :, 3, :, 3] + m[:, :, :, 3, :, 4] + m[:, :, :, 4, :, 3] + m[:, :, :, 4, :, 4])
+
+
+def ref_embed_tokens(idx, table, pe):
+    """idx [n_tok] (rows of Lc = pe.shape[0] tokens each) -> table[idx] + pe[token % Lc], fp64 [n_tok, D]"""
+    Lc = pe.shape[0]
+    pos = torch.arange(idx.numel(), device=idx.device) % Lc
+    return _d(table)[idx.long().reshape(-1)] + _d(pe)[pos]
+
+
 def decode_q8(q8, n_cols, fixed=None):
     """an Mx8Act -> fp32 [M, n_cols]; fixed = (first column, multiplier): columns from there on are e4m3(v * multiplier)"""
     dec = mx8_ref.decode(q8.data[:, :n_cols].contiguous(), q8.scale)
@@ -296,8 +348,10 @@ class Shadow:
         self._launch_calls: list = []    # (op, shape, launches in classes 0..3)
         self.families = defaultdict(int)
         self.family_worst = defaultdict(lambda: {"elem": 0.0, "blk": 0.0})
+        self.op_families = defaultdict(int)      # (op, family) -> traced launches: which plan served which ops function
         self.unchecked_launches = 0
         self.traced = 0
+        self.seen = defaultdict(int)     # (op, shape note) -> comparisons; (op, "call") -> checked calls of that op
 
     # ---------------------------------------------------------------------------------------------------- patching
     def __enter__(self):
@@ -337,6 +391,7 @@ class Shadow:
                 for r in rows[i:i + n]:
                     fam = r[2].split(" ")[0] if r[2] else op            # (untagged launches: the op's name)
                     self.families[fam] += 1
+                    self.op_families[(op, fam)] += 1
                     fw = self.family_worst[fam]
                     fw["elem"], fw["blk"] = max(fw["elem"], res[0]), max(fw["blk"], res[1])
                 if fail is not None:
@@ -370,6 +425,7 @@ class Shadow:
             torch.cuda.synchronize()
             n = self._launch_counts() - before
             self.calls += 1
+            self.seen[(nm, "call")] += 1
             self._cur = [0.0, 0.0, None]
             with torch.no_grad():
                 ref(a, got, live)
@@ -390,6 +446,7 @@ class Shadow:
     # -------------------------------------------------------------------------------------------------- comparison
     def compare(self, what, cls, got, ref, shape_note="", rel_rms=None):
         rtol, atol, k = CLASSES[cls]
+        self.seen[(what.split(" ")[0], shape_note)] += 1
         g = got.to(F64)
         r = ref.to(F64).reshape(g.shape)
         err = (g - r)
@@ -418,6 +475,12 @@ class Shadow:
             msg.append(f"rel RMS {rr:.3e} > {rel_rms:g}")
         if msg:
             self._fail(f"{what} {shape_note} [{cls}]: " + "; ".join(msg))
+
+    def saw(self, op, pred=None):
+        """how many comparisons of ``op`` were made (``pred``: on a shape note it accepts); without ``pred``: checked calls of it"""
+        if pred is None:
+            return self.seen.get((op, "call"), 0)
+        return sum(n for (o, note), n in self.seen.items() if o == op and note != "call" and pred(note))
 
     def _fail(self, m):
         if self._cur[2] is None:
@@ -668,6 +731,13 @@ class Shadow:
             self.check_q8(f"attention_mx8 {note}", q8, got.reshape(M, C), C, ref_is_twin=True)
             self._note_q8(q8, got.reshape(M, C))
 
+    def _ref_masked_attention(self, a, got, live):
+        q, k, v, mask, kpm = a["q"], a["k"], a["v"], a["mask"], a["key_padding_mask"]
+        ref = ref_masked_attention(q, k, v, a["heads"], a["scale"], mask=mask, key_padding_mask=kpm)
+        note = (f"B={q.shape[0]} Nq={q.shape[1]} Lk={k.shape[1]} H={a['heads']} D={q.shape[2] // a['heads']} "
+                f"mask={int(mask is not None)} kpm={int(kpm is not None)}")
+        self.compare("masked_attention", "attn", got, ref, note)
+
     def _ref_tattn_prepare(self, a, got, live):
         # the tables are opaque (MFMA fragment order): they are pinned through tattn_fused, whose reference takes these operands
         self._tables[got.A.untyped_storage().data_ptr()] = (got.A.data_ptr(), got.A.stride(0) * got.A.element_size(), a)
@@ -709,6 +779,17 @@ class Shadow:
 
     def _ref_timestep_embedding(self, a, got, live):
         self.compare("timestep_embedding", "elementwise", got, ref_timestep_embedding(a["t"], a["dim"]), f"n={a['t'].numel()}")
+
+    def _ref_posterior_sample(self, a, got, live):
+        mom = a["moments"]
+        self.compare("posterior_sample", "f32", got, ref_posterior_sample(mom, a["noise"], a["scale"]), f"{tuple(mom.shape)}")
+
+    def _ref_mask_downsample(self, a, got, live):
+        self.compare("mask_downsample", "f32", got, ref_mask_downsample(a["mask"]), f"{tuple(a['mask'].shape)}")
+
+    def _ref_embed_tokens(self, a, got, live):
+        self.compare("embed_tokens", "elementwise", got, ref_embed_tokens(a["idx"], a["table"], a["pe"]),
+                     f"n={a['idx'].numel()} Lc={a['pe'].shape[0]} D={a['pe'].shape[1]}")
 
     def _ref_unet_input(self, a, got, live):
         x, xin0 = a["x"], a["xin"]
@@ -757,6 +838,8 @@ class Shadow:
                 fw = self.family_worst[fam]
                 f.write(f"  family {fam:22s} launches {self.families[fam]:5d} worst elem {fw['elem']:.3e} (tol 1.0) "
                         f"worst block/k {fw['blk']:.3e} (tol 1.0)\n")
+            if self.op_families:
+                f.write("  plans " + ", ".join(f"{op}:{fam} {n}" for (op, fam), n in sorted(self.op_families.items())) + "\n")
 
 
 def _clone(v):

@@ -226,3 +226,167 @@ def test_block_localisation_catches_one_wrong_tile():
     e2 = torch.zeros_like(ref2)
     e2[:32, :32] = 1e-3
     assert S.block_ratio(e2, ref2) == pytest.approx(1e-2, rel=2e-2)
+
+
+# ------------------------------------------------------------ masked_attention, posterior_sample, mask_downsample, embed_tokens
+def _shadow_verdict(cls, got, ref, rel_rms=None):
+    """what Shadow.compare says about one output (None: within its bounds)"""
+    sh = S.Shadow("cpu")
+    sh._cur = [0.0, 0.0, None]
+    sh.compare("op", cls, got, ref, "", rel_rms=rel_rms)
+    return sh._cur[2]
+
+
+def _mattn_inputs(seed, B=3, Nq=9, Lk=11, heads=4, D=32, dtype=D):
+    g = _g(seed)
+    C = heads * D
+    q = torch.randn((B, Nq, C), generator=g, dtype=dtype)
+    kv = torch.randn((B, Lk, 2 * C + 16), generator=g, dtype=dtype)         # (row views wider than heads * D)
+    mask = torch.zeros((Nq, Lk), dtype=torch.float32)
+    mask[torch.rand((Nq, Lk), generator=g) < 0.3] = float("-inf")
+    mask[:, 0] = 0.0                                                         # every query keeps one key
+    kpm = torch.rand((B, Lk), generator=g) < 0.3
+    kpm[:, 0] = False
+    kpm[1, 1:4] = True
+    return q, kv[..., :C], kv[..., C:2 * C + 16], mask, kpm, heads, D
+
+
+def _sdpa_masked(q, k, v, heads, D, scale, mask, kpm):
+    B, Nq = q.shape[:2]
+    split = lambda t: t[..., :heads * D].reshape(B, -1, heads, D).transpose(1, 2)   # noqa: E731
+    merged = None
+    if mask is not None or kpm is not None:
+        merged = torch.zeros((B, 1, Nq, k.shape[1]), dtype=q.dtype)
+        if mask is not None:
+            merged = merged + mask.to(q.dtype)
+        if kpm is not None:
+            merged = merged.masked_fill(kpm[:, None, None, :], float("-inf"))
+    o = F.scaled_dot_product_attention(split(q), split(k), split(v), attn_mask=merged, scale=scale)
+    return o.transpose(1, 2).reshape(B, Nq, heads * D)
+
+
+@pytest.mark.parametrize("use_mask,use_kpm", [(False, False), (True, False), (False, True), (True, True)])
+def test_masked_attention_reference_against_sdpa_with_a_merged_mask(use_mask, use_kpm):
+    q, k, v, mask, kpm, heads, Dh = _mattn_inputs(12)
+    mask, kpm = (mask if use_mask else None), (kpm if use_kpm else None)
+    got = S.ref_masked_attention(q, k, v, heads, Dh ** -0.5, mask=mask, key_padding_mask=kpm)
+    torch.testing.assert_close(got, _sdpa_masked(q, k, v, heads, Dh, Dh ** -0.5, mask, kpm), rtol=1e-10, atol=1e-10)
+    # uint8 key-padding masks (what the kernel is handed) mean the same
+    if use_kpm:
+        torch.testing.assert_close(S.ref_masked_attention(q, k, v, heads, Dh ** -0.5, mask=mask, key_padding_mask=kpm.to(torch.uint8)), got)
+
+
+def test_shadow_rejects_a_key_padding_mask_ignored_for_one_sample():
+    q, k, v, mask, kpm, heads, Dh = _mattn_inputs(13, dtype=torch.float32)
+    q, k, v = q.bfloat16(), k.bfloat16(), v.bfloat16()
+    ref = S.ref_masked_attention(q, k, v, heads, Dh ** -0.5, mask=mask, key_padding_mask=kpm)
+    right = _sdpa_masked(q.float(), k.float(), v.float(), heads, Dh, Dh ** -0.5, mask, kpm).bfloat16()
+    kpm_wrong = kpm.clone()
+    kpm_wrong[1] = False                                                     # sample 1 attends to its padded keys
+    wrong = _sdpa_masked(q.float(), k.float(), v.float(), heads, Dh, Dh ** -0.5, mask, kpm_wrong).bfloat16()
+    assert _shadow_verdict("attn", right, ref) is None
+    assert _shadow_verdict("attn", wrong, ref) is not None
+    assert torch.equal(wrong[0], right[0]) and torch.equal(wrong[2], right[2])          # (only that sample differs)
+
+
+def _moments(B, h, w, ld, seed):
+    """moments as the VAE encoder's quant_conv leaves them: mean of a few units, log-variance mostly small, some at the clamps"""
+    g = _g(seed)
+    mom = torch.randn((B, h, w, ld), generator=g) * 3.0
+    mom[..., 4:8] = torch.randn((B, h, w, 4), generator=g) * 6.0 - 4.0
+    mom[0, 0, :4, 4:8] = torch.tensor([-40.0, 25.0, -30.0, 20.0])
+    noise = torch.randn((B, 4, h, w), generator=g)
+    return mom, noise
+
+
+def _posterior_f32(mom, noise, scale, c_logvar=4):
+    mean = mom[..., :4].permute(0, 3, 1, 2)
+    logvar = mom[..., c_logvar:c_logvar + 4].permute(0, 3, 1, 2).clamp(-30, 20)
+    return scale * (mean + torch.exp(0.5 * logvar) * noise)
+
+
+@pytest.mark.parametrize("ld", [8, 64])
+def test_posterior_sample_reference(ld):
+    mom, noise = _moments(2, 6, 10, ld, 14)
+    got = S.ref_posterior_sample(mom, noise, 0.18215)
+    assert got.shape == (2, 4, 6, 10) and got.dtype == D
+    m = mom.double()
+    want = torch.empty_like(got)
+    for c in range(4):                                                       # indexing, one channel at a time
+        want[:, c] = 0.18215 * (m[..., c] + torch.exp(0.5 * m[..., 4 + c].clamp(-30, 20)) * noise.double()[:, c])
+    torch.testing.assert_close(got, want, rtol=1e-14, atol=1e-14)
+
+
+def test_shadow_rejects_a_posterior_sample_reading_logvar_from_the_wrong_channel():
+    """a kernel that takes the log-variance from the second half of the row (ld / 2 + c) is right at ld = 8 and wrong at ld = 64"""
+    for ld in (8, 64):
+        mom, noise = _moments(2, 16, 24, ld, 15)
+        ref = S.ref_posterior_sample(mom, noise, 0.18215)
+        assert _shadow_verdict("f32", _posterior_f32(mom, noise, 0.18215), ref) is None
+        wrong = _posterior_f32(mom, noise, 0.18215, c_logvar=ld // 2)
+        assert (_shadow_verdict("f32", wrong, ref) is None) == (ld == 8)
+
+
+@pytest.mark.parametrize("H,W", [(64, 64), (64, 96), (256, 384)])
+def test_mask_downsample_reference_is_bilinear_one_eighth(H, W):
+    g = _g(16)
+    mask = torch.rand((2, 1, H, W), generator=g, dtype=D)                      # (not only binary masks)
+    got = S.ref_mask_downsample(mask)
+    assert got.shape == (2, 1, H // 8, W // 8)
+    torch.testing.assert_close(got, F.interpolate(mask, scale_factor=0.125, mode="bilinear"), rtol=1e-12, atol=1e-12)
+
+
+def test_shadow_rejects_a_mask_downsample_with_h_and_w_swapped():
+    g = _g(17)
+    H, W = 256, 384
+    mask = (torch.rand((2, 1, H, W), generator=g) > 0.5).float()
+    ref = S.ref_mask_downsample(mask)
+    right = F.interpolate(mask, scale_factor=0.125, mode="bilinear")
+    # the wrong kernel walks the same memory as W rows of H pixels and writes W/8 rows of H/8
+    wrong = F.interpolate(mask.reshape(2, 1, W, H), scale_factor=0.125, mode="bilinear").reshape(2, 1, H // 8, W // 8)
+    assert _shadow_verdict("f32", right, ref) is None
+    assert _shadow_verdict("f32", wrong, ref) is not None
+    # ... and is invisible on a square mask
+    sq = (torch.rand((2, 1, 256, 256), generator=g) > 0.5).float()
+    assert _shadow_verdict("f32", F.interpolate(sq.reshape(2, 1, 256, 256), scale_factor=0.125, mode="bilinear"),
+                           S.ref_mask_downsample(sq)) is None
+
+
+def test_embed_tokens_reference_and_the_wrong_sequence_length():
+    g = _g(18)
+    B, Lc, Dm = 4, 12, 256
+    idx = torch.randint(0, 95, (B * Lc,), generator=g, dtype=torch.int32)
+    table = torch.randn((95, Dm), generator=g)
+    pe = torch.randn((Lc, Dm), generator=g)
+    ref = S.ref_embed_tokens(idx, table, pe)
+    want = (table.double()[idx.long()].reshape(B, Lc, Dm) + pe.double()[None]).reshape(B * Lc, Dm)
+    torch.testing.assert_close(ref, want, rtol=0, atol=0)
+    right = (table[idx.long()] + pe.repeat(B, 1)).bfloat16()
+    pos_wrong = torch.arange(B * Lc) % 16 % Lc                                # (position modulo 16, not 12: wrong from the second row on)
+    wrong = (table[idx.long()] + pe[pos_wrong]).bfloat16()
+    assert _shadow_verdict("elementwise", right, ref) is None
+    assert _shadow_verdict("elementwise", wrong, ref) is not None
+    assert torch.equal(wrong[:Lc], right[:Lc])
+
+
+def test_f32_class_localisation_factor():
+    """k of the "f32" class comes from the reference side: the worst 32 x 32 block ratio of a float32 torch restatement of
+    posterior_sample and mask_downsample against the float64 references, at the shapes the shadow runs produce, times 8 (another
+    operation order, a fast exp).  The value in CLASSES must be that, up to what another host's float32 exp changes (a factor 1.5)."""
+    worst = 0.0
+    for i, (B, h, w) in enumerate([(4, 64, 64), (1, 32, 48), (2, 32, 48)]):
+        mom, noise = _moments(B, h, w, 8, 20 + i)
+        ref = S.ref_posterior_sample(mom, noise, 0.18215)
+        r = S.block_ratio(_posterior_f32(mom, noise, 0.18215).double() - ref, ref)
+        print(f"posterior_sample {B}x{h}x{w}: float32 restatement block ratio {r:.3e}")
+        worst = max(worst, r)
+    for i, (B, H, W) in enumerate([(4, 512, 512), (2, 256, 384)]):
+        from udifftext_amd import synth
+        mask = synth.synthetic_batch(B, H, W, 9, seed=i)["mask"]
+        ref = S.ref_mask_downsample(mask)
+        r = S.block_ratio(F.interpolate(mask, scale_factor=0.125, mode="bilinear").double() - ref, ref)
+        print(f"mask_downsample {B}x{H}x{W}: float32 restatement block ratio {r:.3e}")
+        worst = max(worst, r)
+    k = S.CLASSES["f32"][2]
+    print(f"worst {worst:.3e} x 8 = {8 * worst:.3e}; CLASSES k {k:g}")
+    assert 8 * worst / 1.5 <= k <= 8 * worst * 1.5
