@@ -125,7 +125,12 @@ typedef struct {
   int32_t ksize;        /* 1 or 3                                                                 */
   int32_t stride;       /* 1 or 2                                                                 */
   int32_t pad_t, pad_l; /* zero padding before the first row / column (bottom/right implicit)     */
-  int32_t upsample;     /* 1: sources are read through a nearest x2 upsample                      */
+  int32_t upsample;     /* 1: sources are read through a nearest x2 upsample
+                           2: the same result as four 2x2 phase convolutions of the low-resolution map (3x3 / stride 1 /
+                              pad 1 only): `w` is the up4 layout bf16 [4][rows][ldw], phase 2a+b of output pixel
+                              (2i+a, 2j+b), k = (2r+s)*C1 + c over low-resolution pixel (i-1+a+r, j-1+b+s), weights
+                              summed over the duplicated taps; ldw (0 = 4*C1) counts ITS row, stride_w (0 = N*ldw) the
+                              elements between phases, K stays 9*C1.  Ask udt_gemm_up4_ok first.                        */
   int32_t rows_per_batch; /* rows of M belonging to one sample (rowvec / transposed addressing)   */
   int32_t ld_rowvec;    /* elements between rows of rowvec (0 = N)                                 */
   int32_t flags;
@@ -194,6 +199,9 @@ int32_t udt_gemm_q8_ok(const udt_gemm_desc* d);
 int32_t udt_gemm_colstats_slots(const udt_gemm_desc* d);
 /* 1 if udt_gemm accepts `in_scsh` for this problem (patch-staged 3x3 convolution geometry; one or two NHWC sources). */
 int32_t udt_gemm_in_scsh_ok(const udt_gemm_desc* d);
+/* 1 if udt_gemm serves this descriptor in the phase form (upsample = 2), else 0: the caller then sets upsample = 1 and passes the
+ * 3x3 weights (fewer than 128 output channels, C1 not a multiple of 64, two sources, in_scsh, fp32 output, maps that do not tile). */
+int32_t udt_gemm_up4_ok(const udt_gemm_desc* d);
 /* The north star's fused block under its own name: GroupNorm(+SiLU) applied on the staged input patch -> 3x3 conv ->
  * epilogue (bias, time-embedding row vector, residual) -> optional statistics of the output.  Same as udt_gemm with a
  * descriptor that has UDT_GEMM_CONV, ksize 3, stride 1, pad 1 and in_scsh set; anything else is UDT_ERR_BAD_ARG. */

@@ -1046,8 +1046,14 @@ bool lean_conv_plan(const udt_gemm_desc* d, lg::C3Params& c, bool want_stats) {
   if (d->C2 != 0 || d->in_scsh || d->colscale || d->batch > 1) return false;
   if (want_stats && !lean_stats_enabled()) return false;
   if (d->N < 128 || d->N % 8 != 0 || d->C1 <= 0 || d->C1 % 64 != 0) return false;
-  const bool ups = d->upsample != 0;
-  if (d->Hout != (d->Hin << (ups ? 1 : 0)) || d->Wout != (d->Win << (ups ? 1 : 0))) return false;
+  // upsample = 2: the phase form (lean.h PHASE) — `w` is the up4 layout, the tiles live in the LOW-RESOLUTION map on the non-upsampling
+  // geometries, four phases per tile; upsample = 1: the nine-tap instance on the upsampled map (what the phase form does not serve)
+  if (d->upsample != 0 && d->upsample != 1 && d->upsample != 2) return false;
+  const bool phase = d->upsample == 2, ups = d->upsample == 1;
+  const int nph = phase ? 4 : 1;
+  if (d->Hout != (d->Hin << (d->upsample ? 1 : 0)) || d->Wout != (d->Win << (d->upsample ? 1 : 0))) return false;
+  if (phase && d->ldw > 0 && d->ldw < 4 * d->C1) return false;
+  const int Ht = phase ? d->Hin : d->Hout, Wt = phase ? d->Win : d->Wout;      // the map the pixel tiles cut
   // pixel tile: 16 x 8 (two MFMA row tiles per wave), or 8 x 8 for the small maps (8 x 8, 24 x 24, ...); 16 x 16 pixels x 160
   // channels on the wide kernel (wide.h: one workgroup per CU) when its tiles — cut into channel-chunk slices where needed —
   // give every CU a unit
@@ -1061,10 +1067,10 @@ bool lean_conv_plan(const udt_gemm_desc* d, lg::C3Params& c, bool want_stats) {
     // that shares the device with s - 1 other streams (cu_share) aims at its share of the CUs: the two CFG halves of a lone batch
     // run 128 tiles each, side by side
     const int wm = wide_conv_mode();
-    if (wm != 0 && !ups && d->N % 160 == 0 && d->Wout % 16 == 0 && d->Hout % 16 == 0) {
+    if (wm != 0 && !ups && d->N % 160 == 0 && Wt % 16 == 0 && Ht % 16 == 0) {
       const int cus = device_cus(), share = d->cu_share > 1 ? d->cu_share : 1;
       wide_slots = cus / share > 0 ? cus / share : 1;
-      const long long wt = (long long)(d->M / 256) * (d->N / 160);
+      const long long wt = (long long)(d->M / 256) * (d->N / 160);         // (phase form: M / 4 / 256 tiles x 4 phases — the same count)
       const long long sk = conv_chunk_slices(wt, wide_slots, d->C1 / 64, lean_splitk_knob());
       const long long units = wt * sk;
       const long long rounds = (units + cus - 1) / cus;
@@ -1072,15 +1078,20 @@ bool lean_conv_plan(const udt_gemm_desc* d, lg::C3Params& c, bool want_stats) {
       // round 6: with three or more batches in flight a launch that fills only 3/4 of its share still goes wide — the 16 x 16 level's
       // 64 whole tiles (one per CU for all 20 channel chunks, no slab exchange) against 160 lean workgroups: +1.2 % images/s
       // (profiles/r06_ab_wide_conv_16x16_under_lanes.txt); alone (four slices per tile) the lean kernel stays 3 us ahead
+      // (phase form, same rule: 16x16 -> 32x32 on 8 samples = 256 whole tiles, one per CU, 86 us against 110 on the lean instance; 32x32 ->
+      //  64x64 = 512, 96 against 98 — tools/bench_gather_convs.py phase, profiles/upconv_phase_shapes.txt)
       wide = (wm > 0) || (sk <= 2 && eff >= ((share >= 3 && share_of(d) >= 3) ? wide_lanes_eff() : 0.85));
     }
   }
-  if (wide) { c.geo = 3; c.tw = 16; c.th = 16; c.bn = 160; c.wgm = 4; }
-  else if (d->Wout % 16 == 0 && d->Hout % 8 == 0) { c.geo = ups ? 2 : 0; c.tw = 16; c.th = 8; }
-  else if (!ups && d->Wout % 8 == 0 && d->Hout % 8 == 0) { c.geo = 1; c.tw = 8; c.th = 8; }
+  if (wide) { c.geo = phase ? 6 : 3; c.tw = 16; c.th = 16; c.bn = 160; c.wgm = 4; }
+  else if (Wt % 16 == 0 && Ht % 8 == 0) { c.geo = ups ? 2 : phase ? 4 : 0; c.tw = 16; c.th = 8; }
+  else if (!ups && Wt % 8 == 0 && Ht % 8 == 0) { c.geo = phase ? 5 : 1; c.tw = 8; c.th = 8; }
   else return false;
   if (d->ldo % 8 != 0 || (d->residual && d->ldr % 8 != 0)) return false;
-  const long long ldw = d->ldw > 0 ? d->ldw : d->K;
+  const long long ldw = d->ldw > 0 ? d->ldw : (phase ? 4LL * d->C1 : (long long)d->K);
+  if (ldw % 8 != 0) return false;
+  c.w_phase = phase ? (d->stride_w > 0 ? d->stride_w : (long long)d->N * ldw) : 0;
+  if (phase && (c.w_phase < (long long)d->N * ldw || c.w_phase % 8 != 0)) return false;
   if ((long long)d->M * d->C1 * 2 >= (1LL << 31) || (long long)d->N * ldw * 2 >= (1LL << 31)) return false;
   if ((reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->residual) | reinterpret_cast<uintptr_t>(d->bias) |
        reinterpret_cast<uintptr_t>(d->rowvec)) & 15) return false;
@@ -1092,20 +1103,23 @@ bool lean_conv_plan(const udt_gemm_desc* d, lg::C3Params& c, bool want_stats) {
   c.N = d->N; c.C = d->C1; c.H = d->Hin; c.W = d->Win; c.B = d->M / (d->Hout * d->Wout);
   c.ldw = (int)ldw; c.ldo = d->ldo; c.ldr = d->ldr; c.ldrv = d->ld_rowvec > 0 ? d->ld_rowvec : d->N;
   c.alpha = d->alpha;
-  c.tiles_x = d->Wout / c.tw; c.tiles_y = d->Hout / c.th;
+  c.tiles_x = Wt / c.tw; c.tiles_y = Ht / c.th;
   c.tiles_m = c.B * c.tiles_x * c.tiles_y;
   c.tiles_n = (d->N + c.bn - 1) / c.bn;
   c.tiles = c.tiles_m * c.tiles_n;
   c.chunks = c.C / 64;
-  const int slots = c.geo == 3 ? wide_slots : (2 * device_cus() / share_of(d) > 0 ? 2 * device_cus() / share_of(d) : 1);
-  int sk = conv_chunk_slices(c.tiles, slots, c.chunks, lean_splitk_knob());
-  while (sk > 1 && (long long)c.tiles * sk * c.tw * c.th * c.bn * 4 > (64LL << 20)) --sk;       // slabs stay inside the workspace
+  const int slots = wide ? wide_slots : (2 * device_cus() / share_of(d) > 0 ? 2 * device_cus() / share_of(d) : 1);
+  // (phase form: c.tiles counts one phase's tiles; the slices are cut for all nph * tiles units, each with its own ticket — 4 taps
+  //  per chunk there, so a slice of >= 4 chunks is 16 taps: the 16x16 -> 32x32 level of a UNet call on 8 samples has 8 * 2 * 10 * 4 =
+  //  640 units and needs none)
+  int sk = conv_chunk_slices((long long)c.tiles * nph, slots, c.chunks, lean_splitk_knob());
+  while (sk > 1 && (long long)c.tiles * nph * sk * c.tw * c.th * c.bn * 4 > (64LL << 20)) --sk;       // slabs stay inside the workspace
   c.ch_per = (c.chunks + sk - 1) / sk;
   c.splitk = (c.chunks + c.ch_per - 1) / c.ch_per;
-  c.G = round_workgroups(c.tiles * c.splitk);
+  c.G = round_workgroups(c.tiles * nph * c.splitk);
   // tile order: ~64 concurrently resident tiles per XCD; n_block weight tiles per patch (conv3p's rule)
   {
-    const double patch = (double)((ups ? c.tw / 2 : c.tw) + 2) * ((ups ? c.th / 2 : c.th) + 2) * c.C * 2.0, wtile = 9.0 * c.bn * c.C * 2.0;
+    const double patch = (double)((ups ? c.tw / 2 : c.tw) + 2) * ((ups ? c.th / 2 : c.th) + 2) * c.C * 2.0, wtile = (phase ? 4.0 : 9.0) * c.bn * c.C * 2.0;
     int nb = g_n_block.load(std::memory_order_relaxed);
     if (nb <= 0) nb = (int)(std::sqrt(64.0 * patch / wtile) + 0.5);
     if (nb < 1) nb = 1;
@@ -1118,8 +1132,10 @@ bool lean_conv_plan(const udt_gemm_desc* d, lg::C3Params& c, bool want_stats) {
   return true;
 }
 
+int lean_conv_phases(const lg::C3Params& c) { return c.geo >= 4 ? 4 : 1; }
+
 size_t lean_conv_workspace(const lg::C3Params& c) {
-  return c.splitk > 1 ? G8_HEADER_BYTES + (size_t)c.tiles * c.splitk * c.tw * c.th * c.bn * sizeof(float) : 0;
+  return c.splitk > 1 ? G8_HEADER_BYTES + (size_t)c.tiles * lean_conv_phases(c) * c.splitk * c.tw * c.th * c.bn * sizeof(float) : 0;
 }
 
 // would this problem run on a lean kernel WITH a statistics-emitting epilogue?  (udt_gemm_colstats_rows / _slots, asked by
@@ -1130,7 +1146,7 @@ bool lean_stats_probe(const udt_gemm_desc* d, int& rows, int& slots) {
     lg::C3Params c3;
     if (lean_conv_plan(d, c3, true)) {
       rows = c3.tw * c3.th / c3.wgm;                              // one slot per wave pixel block of a tile
-      slots = c3.tiles_m * c3.wgm;
+      slots = c3.tiles_m * c3.wgm * lean_conv_phases(c3);         // (phase form: [image][phase][tile][wave pixel block])
       return true;
     }
   }
@@ -1212,6 +1228,12 @@ extern "C" int32_t udt_gemm_in_scsh_ok(const udt_gemm_desc* d) {
   if (!d || d->K <= 0 || d->K % BK != 0) return 0;
   c3p::Geo ge;
   return conv3p_geometry(d, ge, true) ? 1 : 0;
+}
+
+extern "C" int32_t udt_gemm_up4_ok(const udt_gemm_desc* d) {
+  if (!d || d->upsample != 2) return 0;
+  lg::C3Params c3;
+  return lean_conv_plan(d, c3, d->colstats != nullptr) ? 1 : 0;
 }
 
 extern "C" int udt_gn_silu_conv3x3_fwd(const udt_gemm_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1346,7 +1368,9 @@ extern "C" int udt_gemm(const udt_gemm_desc* d, void* workspace, size_t workspac
   p.M = d->M; p.N = d->N; p.K = d->K;
   p.lda = d->lda; p.ldo = d->ldo; p.ldr = d->ldr;
   p.ldw = d->ldw > 0 ? d->ldw : d->K;
-  if (p.ldw < d->K || p.ldw % 8 != 0) return UDT_ERR_BAD_SHAPE;
+  if (d->upsample == 2) {                              // phase form: `w` is the up4 layout (rows of 4 C1), served by lean_conv_plan or not at all
+    if (!udt_gemm_up4_ok(d)) return UDT_ERR_BAD_SHAPE;
+  } else if (p.ldw < d->K || p.ldw % 8 != 0) return UDT_ERR_BAD_SHAPE;
   if (mx8 && d->lda < d->K) return UDT_ERR_BAD_SHAPE;
   p.sA = d->stride_a; p.sW = d->stride_w; p.sO = d->stride_out; p.sR = d->stride_res;
   p.Hin = d->Hin; p.Win = d->Win; p.C1 = d->C1; p.C2 = d->C2; p.Hout = d->Hout; p.Wout = d->Wout;
@@ -1422,8 +1446,10 @@ extern "C" int udt_gemm(const udt_gemm_desc* d, void* workspace, size_t workspac
       UdtProfScope profc(cls, s);
       if (profc.rec) {
         char tag[96];
-        snprintf(tag, sizeof(tag), "%s%s M=%d N=%d K=%d %dx%d tile=%dx%d units=%d splitk=%d nb=%d", c3.geo == 3 ? "wconv3" : "lconv3", d->upsample ? "+up" : "", d->M, d->N, d->K,
-                 d->Hin, d->Win, c3.tw, c3.th, c3.tiles * c3.splitk, c3.splitk, c3.n_block);
+        snprintf(tag, sizeof(tag), "%s%s M=%d N=%d K=%d %dx%d tile=%dx%d units=%d splitk=%d nb=%d%s", (c3.geo == 3 || c3.geo == 6) ? "wconv3" : "lconv3",
+                 (d->upsample && c3.geo != 6) ? "+up" : "", d->M, d->N, d->K,
+                 d->Hin, d->Win, c3.tw, c3.th, c3.tiles * lean_conv_phases(c3) * c3.splitk, c3.splitk, c3.n_block,
+                 d->upsample == 2 ? " up4" : "");      // (the first word stays the kernel family — lconv3+up / wconv3 —, the phase form is marked at the end)
         udt_prof_tag(profc.rec, tag);
       }
       const hipError_t ec = udt_lean_launch_conv3(&c3, s);

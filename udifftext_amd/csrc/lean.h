@@ -715,9 +715,17 @@ struct C3Geo {
   static_assert(SMEM <= 80 * 1024, "two workgroups per CU");
 };
 
-template <int TW, int TH, bool UPS, bool STATS = false>
+// PHASE: the same upsampling convolution as four 2 x 2 phase convolutions on the LOW-RESOLUTION map.  Output pixel (2i + a, 2j + b)
+// reads low-resolution rows {i - 1 + a, i + a} and columns {j - 1 + b, j + b} only (the other taps of the 3 x 3 multiply
+// duplicates), so phase (a, b) is a stride-1 pad-1 convolution with the four taps (a + r, b + s), r, s in {0, 1}, of the staged
+// patch, on weights summed over the duplicates (packing.pack_conv_up4: p.w holds [4][N rows][4 C], phase 2a + b, p.w_phase elements
+// apart, k = (2r + s) C + c), stored at stride 2.  The tile lives in the low-resolution map (the non-UPS geometries); the phase is the
+// outermost factor of the unit index (unit = (phase * tiles + tile) * splitk + slice), tickets and slabs are per (phase, tile).
+template <int TW, int TH, bool UPS, bool STATS = false, bool PHASE = false>
 __global__ void __launch_bounds__(256, 2) lconv3_kernel(const C3Params p) {
+  static_assert(!(UPS && PHASE), "the phase form runs on the low-resolution geometries");
   using Geo = C3Geo<TW, TH, UPS>;
+  constexpr int NT = PHASE ? 4 : 9;                      // taps per channel chunk
   constexpr int NW = 4, TM = Geo::TM, TN = 2, BN = 128, BMPX = Geo::PX;
   constexpr int C3_PW = Geo::PW, C3_PROWS = Geo::PROWS, C3_PIECES = Geo::PIECES, C3_PATCH_BYTES = Geo::PATCH_BYTES;
   constexpr int C3_W_BYTES = Geo::W_BYTES, C3_TW = TW, C3_TH = TH;
@@ -743,9 +751,12 @@ __global__ void __launch_bounds__(256, 2) lconv3_kernel(const C3Params p) {
   const int w_frag_row = (col0 + l31) * ROW_BYTES;
 
   const int unit = range_index(blockIdx.x, p.G);
-  if (unit >= p.tiles * p.splitk) return;
-  const int tile = unit / p.splitk;
-  const int slice = unit - tile * p.splitk;
+  if (unit >= p.tiles * p.splitk * (PHASE ? 4 : 1)) return;
+  const int phase = PHASE ? unit / (p.tiles * p.splitk) : 0;
+  const int pha = phase >> 1, phb = phase & 1;
+  const int ptile = unit / p.splitk;                     // ticket / slab index: (phase, tile)
+  const int slice = unit - ptile * p.splitk;
+  const int tile = ptile - phase * p.tiles;
   int tile_m, n0;
   {
     const int per_block = p.tiles_m * p.n_block;
@@ -766,7 +777,8 @@ __global__ void __launch_bounds__(256, 2) lconv3_kernel(const C3Params p) {
   if (c1 > p.chunks) c1 = p.chunks;
 
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.a), 0, p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.w), 0, p.w_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_w =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.w) + (PHASE ? (long long)phase * p.w_phase : 0LL), 0, p.w_bytes, 0x00020000);
   // XOR swizzle of a patch row's 16-byte slots.  The rows one ds_read_b128 lane group touches are 16 consecutive pixels of
   // one or two image rows; with the patch pitch of TW + 2 rows, (row >> 1) & 7 maps two of them onto the same slot (PMC:
   // a third of the LDS cycles of the first version were bank conflicts).  Keying the swizzle on the row index with the
@@ -800,8 +812,8 @@ __global__ void __launch_bounds__(256, 2) lconv3_kernel(const C3Params p) {
   for (int tm = 0; tm < TM; ++tm) {
     const int ml = row0 + tm * 32 + l31;
     const int py = ml / TW, px = ml - py * TW;
-    a_py[tm] = py;
-    a_prow[tm] = UPS ? (py | (px << 16)) : (py * C3_PW + px);      // patch row of this lane's pixel at tap (0, 0)
+    a_py[tm] = PHASE ? py + pha : py;
+    a_prow[tm] = UPS ? (py | (px << 16)) : PHASE ? ((py + pha) * C3_PW + px + phb) : (py * C3_PW + px);   // patch row of this lane's pixel at tap (0, 0)
   }
   auto issue_w = [&](int st, int c, int tap) {
     const int soff = (tap * p.C + c * 64) * 2;
@@ -825,18 +837,19 @@ __global__ void __launch_bounds__(256, 2) lconv3_kernel(const C3Params p) {
 
   issue_patch(c0);
 #pragma unroll
-  for (int j = 0; j < NR - 1; ++j) issue_w(j, c0, j);     // (a chunk has nine taps >= NR - 1)
+  for (int j = 0; j < NR - 1; ++j) issue_w(j, c0, j);     // (a chunk has NT taps >= NR - 1)
+  static_assert(NR - 1 < NT, "the ring's prologue stays inside the first chunk");
   int st = 0;
   for (int c = c0; c < c1; ++c) {
     const bool nxt = (c + 1 < c1);
     const char* pbuf = patches + (c & 1) * C3_PATCH_BYTES;
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
+    for (int tap = 0; tap < NT; ++tap) {
       // loads younger than this tap's weight tile, in issue order: the NR - 2 tiles after it (fewer at the very end) and,
       // for taps 1 .. NR - 1 of a chunk that has a successor, the next patch (issued at tap 0 behind that tap's tile): they
       // stay in flight, everything older has landed
       {
-        const int w_ahead = nxt ? NR - 2 : ((8 - tap) < NR - 2 ? (8 - tap) : NR - 2);
+        const int w_ahead = nxt ? NR - 2 : ((NT - 1 - tap) < NR - 2 ? (NT - 1 - tap) : NR - 2);
         const bool patch_ahead = nxt && tap >= 1 && tap <= NR - 1;
         wait_vm_upto<(NR - 2) * WP + PP>(w_ahead * WP + (patch_ahead ? PP : 0));   // (folds to one s_waitcnt per tap)
       }
@@ -845,11 +858,11 @@ __global__ void __launch_bounds__(256, 2) lconv3_kernel(const C3Params p) {
         const int ahead = tap + NR - 1;
         int s2 = st + NR - 1;
         if (s2 >= NR) s2 -= NR;
-        if (ahead < 9) issue_w(s2, c, ahead);
-        else if (nxt) issue_w(s2, c + 1, ahead - 9);
+        if (ahead < NT) issue_w(s2, c, ahead);
+        else if (nxt) issue_w(s2, c + 1, ahead - NT);
       }
       if (tap == 0 && nxt && !UDT_DBG(p.dbg, 1)) issue_patch(c + 1);
-      const int dy = tap / 3, dx = tap - dy * 3;
+      const int dy = PHASE ? tap >> 1 : tap / 3, dx = PHASE ? tap & 1 : tap - dy * 3;
       const char* wbuf = wring + st * C3_W_BYTES;
       bf16x8_t fx[4][TM], fw[4][TN];
       if (!UDT_DBG(p.dbg, 3)) {
@@ -911,11 +924,11 @@ __global__ void __launch_bounds__(256, 2) lconv3_kernel(const C3Params p) {
     __syncthreads();
     int* const bcast = reinterpret_cast<int*>(smem);
     if (tid == 0) {
-      const int t = __hip_atomic_fetch_add(p.counters + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int t = __hip_atomic_fetch_add(p.counters + ptile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const int last = (t == p.splitk - 1) ? 1 : 0;
       if (last) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        __hip_atomic_store(p.counters + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(p.counters + ptile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       *bcast = last;
     }
@@ -930,7 +943,7 @@ __global__ void __launch_bounds__(256, 2) lconv3_kernel(const C3Params p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     for (int s = 0; s < p.splitk; ++s) {
-      const f32x4* sl = reinterpret_cast<const f32x4*>(p.slabs + ((long long)tile * p.splitk + s) * (BMPX * BN));
+      const f32x4* sl = reinterpret_cast<const f32x4*>(p.slabs + ((long long)ptile * p.splitk + s) * (BMPX * BN));
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -975,13 +988,15 @@ __global__ void __launch_bounds__(256, 2) lconv3_kernel(const C3Params p) {
     }
   }
   constexpr int NIT = TM * 4;                            // 8 pixel rows per instruction
-  const int Ho = UPS ? 2 * p.H : p.H, Wo = UPS ? 2 * p.W : p.W;
+  const int Ho = (UPS || PHASE) ? 2 * p.H : p.H, Wo = (UPS || PHASE) ? 2 * p.W : p.W;
   long long mrow[NIT];
 #pragma unroll
   for (int i = 0; i < NIT; ++i) {
     const int ml = row0 + i * 8 + rl;
     const int py = ml / TW, px = ml - py * TW;
-    mrow[i] = ((long long)b * Ho + (y0 + py)) * Wo + (x0 + px);
+    // (PHASE: tile pixel (y, x) of the low-resolution map is output pixel (2y + a, 2x + b); a pixel's channel row stays contiguous)
+    mrow[i] = PHASE ? ((long long)b * Ho + (2 * (y0 + py) + pha)) * Wo + (2 * (x0 + px) + phb)
+                    : ((long long)b * Ho + (y0 + py)) * Wo + (x0 + px);
   }
   u32x4 rv[NIT];
   if (p.res) {
@@ -1030,7 +1045,8 @@ __global__ void __launch_bounds__(256, 2) lconv3_kernel(const C3Params p) {
   }
   if constexpr (STATS) {
     // one slot per wave pixel block (WROWS pixels of one image); the two waves that share the pixels cover different channels
-    const int slot = tile_m * 2 + wm;
+    // (PHASE: a sample's slots stay consecutive: [image][phase][tile of the image][wave pixel block])
+    const int slot = (PHASE ? (b * 4 + phase) * per_img + rt : tile_m) * 2 + wm;
     wave_colstats<8, 8>(wl, lane, cs, cq, p.colstats + ((long long)slot * p.N + n) * 2, col_ok);
   }
 }

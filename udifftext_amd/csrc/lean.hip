@@ -67,27 +67,27 @@ hipError_t launch_lean_mx8(const lg::LParams& lp, int smem, int G, bool geglu, b
   return emit ? launch_lean_mx8_k<false, false, false, true, true>(lp, smem, G, s) : launch_lean_mx8_k<false, false, false, true, false>(lp, smem, G, s);
 }
 
-template <int TW, int TH, bool UPS, bool STATS>
+template <int TW, int TH, bool UPS, bool STATS, bool PHASE>
 hipError_t launch_lconv3s(const lg::C3Params& c3, hipStream_t s) {
   static AttrOnce once;
   constexpr int smem = lg::C3Geo<TW, TH, UPS>::SMEM;
-  hipError_t e = once.ensure(reinterpret_cast<const void*>(lg::lconv3_kernel<TW, TH, UPS, STATS>), smem);
+  hipError_t e = once.ensure(reinterpret_cast<const void*>(lg::lconv3_kernel<TW, TH, UPS, STATS, PHASE>), smem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((lg::lconv3_kernel<TW, TH, UPS, STATS>), dim3(c3.G), dim3(256), smem, s, c3);
+  hipLaunchKernelGGL((lg::lconv3_kernel<TW, TH, UPS, STATS, PHASE>), dim3(c3.G), dim3(256), smem, s, c3);
   return hipGetLastError();
 }
-template <int TW, int TH, bool UPS>
+template <int TW, int TH, bool UPS, bool PHASE = false>
 hipError_t launch_lconv3(const lg::C3Params& c3, hipStream_t s) {
-  return c3.colstats ? launch_lconv3s<TW, TH, UPS, true>(c3, s) : launch_lconv3s<TW, TH, UPS, false>(c3, s);
+  return c3.colstats ? launch_lconv3s<TW, TH, UPS, true, PHASE>(c3, s) : launch_lconv3s<TW, TH, UPS, false, PHASE>(c3, s);
 }
 
-template <bool STATS>
+template <bool STATS, bool PHASE>
 hipError_t launch_wconv3s(const lg::C3Params& c3, hipStream_t s) {
   static AttrOnce once;
   constexpr int smem = wd::WGeo::SMEM;
-  hipError_t e = once.ensure(reinterpret_cast<const void*>(wd::wconv3_kernel<STATS>), smem);
+  hipError_t e = once.ensure(reinterpret_cast<const void*>(wd::wconv3_kernel<STATS, PHASE>), smem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((wd::wconv3_kernel<STATS>), dim3(c3.G), dim3(256), smem, s, c3);
+  hipLaunchKernelGGL((wd::wconv3_kernel<STATS, PHASE>), dim3(c3.G), dim3(256), smem, s, c3);
   return hipGetLastError();
 }
 template <int KT, bool GEGLU, bool EMIT = false>
@@ -100,8 +100,9 @@ hipError_t launch_rowres(const lg::LParams& lp, int G, hipStream_t s) {
   return hipGetLastError();
 }
 
+template <bool PHASE>
 hipError_t launch_wconv3(const lg::C3Params& c3, hipStream_t s) {
-  return c3.colstats ? launch_wconv3s<true>(c3, s) : launch_wconv3s<false>(c3, s);
+  return c3.colstats ? launch_wconv3s<true, PHASE>(c3, s) : launch_wconv3s<false, PHASE>(c3, s);
 }
 
 }  // namespace
@@ -124,6 +125,7 @@ hipError_t udt_lean_launch_gemm(int cfg, const void* lparams, int smem, int G, i
 
 hipError_t udt_lean_launch_conv3(const void* c3params, hipStream_t s) {
   const lg::C3Params& c3 = *static_cast<const lg::C3Params*>(c3params);
-  return c3.geo == 3 ? launch_wconv3(c3, s) : c3.geo == 2 ? launch_lconv3<16, 8, true>(c3, s)
+  return c3.geo == 3 ? launch_wconv3<false>(c3, s) : c3.geo == 6 ? launch_wconv3<true>(c3, s) : c3.geo == 2 ? launch_lconv3<16, 8, true>(c3, s)
+         : c3.geo == 4 ? launch_lconv3<16, 8, false, true>(c3, s) : c3.geo == 5 ? launch_lconv3<8, 8, false, true>(c3, s)
          : c3.geo == 1 ? launch_lconv3<8, 8, false>(c3, s) : launch_lconv3<16, 8, false>(c3, s);
 }

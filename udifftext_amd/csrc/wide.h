@@ -53,9 +53,12 @@ struct WGeo {
   static_assert(SMEM <= 160 * 1024, "one workgroup per CU");
 };
 
-template <bool STATS>
+// PHASE: nearest x2 upsample + 3x3 as four 2x2 phase convolutions of the low-resolution map (lean.h lconv3_kernel PHASE: same unit
+// order, weight layout, tickets and statistics slots): four taps per chunk, so the next chunk's patch is requested over taps 0 and 1.
+template <bool STATS, bool PHASE = false>
 __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
   using G = WGeo;
+  constexpr int NT = PHASE ? 4 : 9;                          // taps per channel chunk
   constexpr int NW = G::NW, TM = G::TM, TN = G::TN, BN = G::BN, PW = G::PW, NR = G::NRING;
   constexpr int WP = (BN / 8) / NW;                          // weight pieces per wave and tap (5)
   constexpr int PP = (G::PIECES + NW - 1) / NW;              // patch pieces per wave and chunk (11, padded with duplicates)
@@ -77,9 +80,12 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
   const int w_frag_row = l31 * ROW_BYTES;
 
   const int unit = range_index(blockIdx.x, p.G);
-  if (unit >= p.tiles * p.splitk) return;
-  const int tile = unit / p.splitk;
-  const int slice = unit - tile * p.splitk;
+  if (unit >= p.tiles * p.splitk * (PHASE ? 4 : 1)) return;
+  const int phase = PHASE ? unit / (p.tiles * p.splitk) : 0;
+  const int pha = phase >> 1, phb = phase & 1;
+  const int ptile = unit / p.splitk;                         // ticket / slab index: (phase, tile)
+  const int slice = unit - ptile * p.splitk;
+  const int tile = ptile - phase * p.tiles;
   int tile_m, n0;
   {
     const int per_block = p.tiles_m * p.n_block;
@@ -100,7 +106,8 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
   if (c1 > p.chunks) c1 = p.chunks;
 
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.a), 0, p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.w), 0, p.w_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_w =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.w) + (PHASE ? (long long)phase * p.w_phase : 0LL), 0, p.w_bytes, 0x00020000);
   // patch rows: 16-byte slots XOR-swizzled on the row index with the halo pitch removed (lean.h lconv3_kernel: the rows one
   // ds_read_b128 lane group touches are 16 consecutive pixels of one image row — same tile width here)
   auto patch_swz = [](int prow, int yy) { return ((prow - 2 * yy) >> 1) & 7; };
@@ -131,8 +138,8 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
   for (int tm = 0; tm < TM; ++tm) {
     const int ml = row0 + tm * 32 + l31;
     const int py = ml / G::TW, px = ml - py * G::TW;
-    a_py[tm] = py;
-    a_prow[tm] = py * PW + px;                               // patch row of this lane's pixel at tap (0, 0)
+    a_py[tm] = PHASE ? py + pha : py;
+    a_prow[tm] = PHASE ? (py + pha) * PW + px + phb : py * PW + px;      // patch row of this lane's pixel at tap (0, 0)
   }
   auto issue_w = [&](int st, int c, int tap) {
     const int soff = (tap * p.C + c * 64) * 2;
@@ -154,9 +161,10 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  // patch pieces of the NEXT chunk are requested two per tap (taps 0 .. 5), behind the tap's weight tile
-  constexpr int PPT = 2, PTAPS = (PP + PPT - 1) / PPT;       // 11 pieces = 5 x 2 + 1
-  static_assert(PTAPS <= 7, "the next patch is complete two taps before its chunk starts");
+  // patch pieces of the NEXT chunk are requested two per tap (taps 0 .. 5; PHASE: six per tap, taps 0 and 1), behind the tap's weight tile
+  constexpr int PPT = PHASE ? 6 : 2, PTAPS = (PP + PPT - 1) / PPT;       // 11 pieces = 5 x 2 + 1 (PHASE: 6 + 5)
+  static_assert(PTAPS <= NT - 2, "the next patch is complete two taps before its chunk starts");
+  static_assert(NR - 1 < NT, "the ring's prologue stays inside the first chunk");
   auto issue_patch_part = [&](int buf, int c, int part) {
     char* pbuf = patches + buf * G::PATCH_BYTES;
 #pragma unroll
@@ -170,7 +178,7 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
   for (int j = 0; j < NR - 1; ++j) issue_w(j, c0, j);
   int st = 0;
   for (int c = c0; c < c1; ++c) {
-    // every tap issues the same loads (the scheduler then sees nine straight-line tap bodies): behind the last chunk the
+    // every tap issues the same loads (the scheduler then sees NT straight-line tap bodies): behind the last chunk the
     // "next" weight tiles / patch are re-reads of this chunk into buffers nobody reads again
     const int cn = (c + 1 < c1) ? c + 1 : c;
     const char* pbuf = patches + (c & 1) * G::PATCH_BYTES;
@@ -179,10 +187,10 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
       // loads younger than this tap's weight tile W(t), in issue order: the patch pieces of tap t - 2, W(t + 1), the patch
       // pieces of tap t - 1: they stay in flight, everything older has landed (the first chunk's patch is issued whole in
       // the prologue, ahead of W(0))
-      constexpr auto pcount = [](int t) { const int tt = (t + 9) % 9; return tt < PTAPS ? ((tt + 1) * PPT <= PP ? PPT : PP - tt * PPT) : 0; };
+      constexpr auto pcount = [](int t) { const int tt = (t + NT) % NT; return tt < PTAPS ? ((tt + 1) * PPT <= PP ? PPT : PP - tt * PPT) : 0; };
       wait_vm<pcount(tap - 2) + WP + pcount(tap - 1)>();
       raw_barrier();
-      const int dy = tap / 3, dx = tap - dy * 3;
+      const int dy = PHASE ? tap >> 1 : tap / 3, dx = PHASE ? tap & 1 : tap - dy * 3;
       const char* wbuf = wring + st * G::W_BYTES;
       int arow[TM], aswz[TM];
 #pragma unroll
@@ -213,8 +221,8 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
           int s2 = st + NR - 1;
           if (s2 >= NR) s2 -= NR;
           if (!UDT_DBG(p.dbg, 0)) {
-            if (ahead < 9) issue_w(s2, c, ahead);
-            else issue_w(s2, cn, ahead - 9);
+            if (ahead < NT) issue_w(s2, c, ahead);
+            else issue_w(s2, cn, ahead - NT);
           }
           if constexpr (tap < PTAPS) {
             if (!UDT_DBG(p.dbg, 1)) issue_patch_part((c + 1) & 1, cn, tap);
@@ -243,18 +251,22 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
         }
         __builtin_amdgcn_sched_group_barrier(0x008, TM * TN - (TM + TN), 0);
       }
-      constexpr int NV = WP + pcount(tap);
+      constexpr int NV = WP + pcount(tap), NVI = NV < TM * TN ? NV : TM * TN;      // (PHASE tap 0: 11 requests behind 10 MFMAs)
 #pragma unroll
-      for (int i = 0; i < NV; ++i) {
+      for (int i = 0; i < NVI; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, TM * TN - NV, 0);
+      if constexpr (NV > NVI) __builtin_amdgcn_sched_group_barrier(0x020, NV - NVI, 0);
+      else __builtin_amdgcn_sched_group_barrier(0x008, TM * TN - NV, 0);
       st = (st + 1 == NR) ? 0 : st + 1;
     };
     tap_body(std::integral_constant<int, 0>{}); tap_body(std::integral_constant<int, 1>{}); tap_body(std::integral_constant<int, 2>{});
-    tap_body(std::integral_constant<int, 3>{}); tap_body(std::integral_constant<int, 4>{}); tap_body(std::integral_constant<int, 5>{});
-    tap_body(std::integral_constant<int, 6>{}); tap_body(std::integral_constant<int, 7>{}); tap_body(std::integral_constant<int, 8>{});
+    tap_body(std::integral_constant<int, 3>{});
+    if constexpr (!PHASE) {
+      tap_body(std::integral_constant<int, 4>{}); tap_body(std::integral_constant<int, 5>{});
+      tap_body(std::integral_constant<int, 6>{}); tap_body(std::integral_constant<int, 7>{}); tap_body(std::integral_constant<int, 8>{});
+    }
   }
   // epilogue addressing (a row = one pixel x 160 channels; 20 lanes cover a row, 8 channels each, three rows per instruction)
   // and the residual rows of BOTH 32-pixel passes, requested before the ring drains: their latency overlaps the drain, the
@@ -277,7 +289,8 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
       rok[tm][i] = col_ok && row < 32;
       const int ml = row0 + tm * 32 + (row < 32 ? row : 0);
       const int py = ml / G::TW, px = ml - py * G::TW;
-      mrow[tm][i] = ((long long)b * p.H + (y0 + py)) * p.W + (x0 + px);
+      mrow[tm][i] = PHASE ? ((long long)b * (2 * p.H) + (2 * (y0 + py) + pha)) * (2 * p.W) + (2 * (x0 + px) + phb)
+                          : ((long long)b * p.H + (y0 + py)) * p.W + (x0 + px);
       u32x4 z = {0u, 0u, 0u, 0u};
       rv[tm][i] = z;
       if (p.res && rok[tm][i]) rv[tm][i] = *reinterpret_cast<const u32x4*>(p.res + mrow[tm][i] * p.ldr + n);
@@ -300,11 +313,11 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
     __syncthreads();
     int* const bcast = reinterpret_cast<int*>(smem);
     if (tid == 0) {
-      const int t = __hip_atomic_fetch_add(p.counters + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int t = __hip_atomic_fetch_add(p.counters + ptile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const int last = (t == p.splitk - 1) ? 1 : 0;
       if (last) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        __hip_atomic_store(p.counters + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(p.counters + ptile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       *bcast = last;
     }
@@ -319,7 +332,7 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     for (int s = 0; s < p.splitk; ++s) {
-      const f32x4* sl = reinterpret_cast<const f32x4*>(p.slabs + ((long long)tile * p.splitk + s) * (G::TW * G::TH * BN));
+      const f32x4* sl = reinterpret_cast<const f32x4*>(p.slabs + ((long long)ptile * p.splitk + s) * (G::TW * G::TH * BN));
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -401,7 +414,7 @@ __global__ void __launch_bounds__(256, 1) wconv3_kernel(const C3Params p) {
   }
   if constexpr (STATS) {
     // one slot per wave pixel block (64 pixels of one image)
-    const int slot = tile_m * NW + wave;
+    const int slot = (PHASE ? (b * 4 + phase) * per_img + rt : tile_m) * NW + wave;
     wave_colstats<CPR, RPI>(wl, lane, cs, cq, p.colstats + ((long long)slot * p.N + n) * 2, col_ok);
   }
 }

@@ -80,6 +80,7 @@ SYMBOLS = {
     "udt_gemm_rowstat_parts": (_i32, [C.POINTER(GemmDesc)]),
     "udt_gemm_q8_ok": (_i32, [C.POINTER(GemmDesc)]),
     "udt_gemm_in_scsh_ok": (_i32, [C.POINTER(GemmDesc)]),
+    "udt_gemm_up4_ok": (_i32, [C.POINTER(GemmDesc)]),
     "udt_gn_silu_conv3x3_fwd": (C.c_int, [C.POINTER(GemmDesc), _vp, C.c_size_t, _vp]),
     "udt_ln_gemm_fwd": (C.c_int, [C.POINTER(GemmDesc), _vp, C.c_size_t, _vp]),
     "udt_gn_finalize": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _fp, _fp, _fp, _i32, _i64, _i32, _f32, _vp]),

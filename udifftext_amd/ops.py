@@ -387,9 +387,11 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
            out_hw: Optional[tuple] = None, residual: Optional[torch.Tensor] = None,
            rowvec: Optional[torch.Tensor] = None, flags: int = 0, n_out: Optional[int] = None,
            out: Optional[torch.Tensor] = None, colstats: bool = False, in_scsh: Optional[torch.Tensor] = None,
-           in_act: int = 0, probe_in_scsh: bool = False):
+           in_act: int = 0, probe_in_scsh: bool = False, w_up4: Optional[torch.Tensor] = None):
     """NHWC convolution as implicit GEMM.  x [B,H,W,C1] (+ optional x2 [B,H,W,C2], channel concat) bf16;
     w [N, ksize*ksize*(C1+C2)] packed tap-major.  Returns [B,Hout,Wout,N].
+    w_up4 (with upsample): the same weights in the phase layout [4, N, 4*C1] (packing.pack_conv_up4) — the launch runs as four 2x2
+    phase convolutions of the low-resolution map where the library serves the shape (udt_gemm_up4_ok), else on ``w`` as without it;
     in_scsh / in_act: GroupNorm scale/shift table (gn_finalize) + activation applied to the input on the staged patch
     (udt_gn_silu_conv3x3_fwd); colstats: emit the output's column statistics (``out.gn_stats``);
     probe_in_scsh: no launch — returns whether the library would accept in_scsh for this problem."""
@@ -422,6 +424,13 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
                   ld_rowvec=(rowvec.stride(0) if rowvec is not None else 0), flags=flags | L.GEMM_CONV)
     if probe_in_scsh:
         return bool(L.load().udt_gemm_in_scsh_ok(C.byref(d)))
+    if w_up4 is not None and upsample and ksize == 3 and x2 is None and in_scsh is None:
+        _bf16(w_up4)
+        assert w_up4.is_contiguous() and w_up4.dim() == 3 and w_up4.shape[0] == 4 and w_up4.shape[1] >= N and w_up4.shape[2] == 4 * C1, \
+            (w_up4.shape, N, C1)
+        d.upsample, d.w, d.ldw, d.stride_w = 2, _ptr(w_up4), w_up4.shape[2], w_up4.stride(0)
+        if not L.load().udt_gemm_up4_ok(C.byref(d)):
+            d.upsample, d.w, d.ldw, d.stride_w = 1, _ptr(w), 0, 0
     if in_scsh is not None:                       # (before the statistics probe: the plan depends on it)
         assert in_scsh.dtype == torch.float32 and in_scsh.is_contiguous() and in_scsh.numel() == B * (C1 + C2) * 2
         d.in_scsh = in_scsh.data_ptr()

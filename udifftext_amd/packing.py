@@ -50,6 +50,30 @@ def pack_conv(w: torch.Tensor, segments=None, n_pad_to: int = 4) -> torch.Tensor
     return out.reshape(Np, -1).contiguous()
 
 
+# output row parity a (column parity b) -> the 3x3 taps dy (dx) that land on low-resolution row i - 1 + a + r, r = 0, 1
+UP4_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def pack_conv_up4(w: torch.Tensor, n_pad_to: int = 4) -> torch.Tensor:
+    """[N, Cin, 3, 3] fp32 -> bf16 [4][Npad][4*Cpad]: nearest x2 upsample + conv3x3(pad 1) as four 2x2 phase convolutions of the
+    LOW-RESOLUTION map.  Output pixel (2i + a, 2j + b) is phase 2a + b; its column k = (2r + s)*Cpad + c multiplies channel c of
+    low-resolution pixel (i - 1 + a + r, j - 1 + b + s) (zero outside the map) with the sum of the 3x3 taps that read that pixel
+    through the upsample (UP4_TAPS).  The sums are taken in fp32 over the bf16-ROUNDED taps — what ``pack_conv`` holds and every
+    reference multiplies — and rounded once."""
+    N, Cin, kh, kw = w.shape
+    assert (kh, kw) == (3, 3), "the phase form exists for 3x3 convolutions"
+    Np, Cp = _round_up(N, n_pad_to), pad_channels(Cin)
+    wb = w.to(torch.bfloat16).float()
+    out = torch.zeros((4, Np, 2, 2, Cp), dtype=torch.bfloat16, device=w.device)
+    for a in range(2):
+        for b in range(2):
+            for r in range(2):
+                for s in range(2):
+                    v = sum(wb[:, :, dy, dx] for dy in UP4_TAPS[a][r] for dx in UP4_TAPS[b][s])
+                    out[2 * a + b, :N, r, s, :Cin] = v.to(torch.bfloat16)
+    return out.reshape(4, Np, 4 * Cp).contiguous()
+
+
 def pad_bias(b: torch.Tensor | None, n_pad_to: int = 4) -> torch.Tensor | None:
     if b is None:
         return None

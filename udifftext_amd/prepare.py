@@ -69,6 +69,8 @@ def prepare(engine, free_masters: bool = False, dedup_vae: bool = True) -> Dict[
             seen.add(id(m))
             report["packed_modules"] += 1
             report["packed_bytes"] += H.nbytes(m.packed())
+            if getattr(m, "upsamples", False):          # Upsample.conv: the phase layout of its 3x3 weights
+                report["packed_bytes"] += H.nbytes(m.packed_up4())
         report["packed_bytes"] += H.nbytes(unet._emb_pack())
         # ---- LayerNorm-folded layouts of the q|k|v and GEGLU projections (udt_ln_gemm_fwd)
         from sgm.modules.attention import BasicTransformerBlock

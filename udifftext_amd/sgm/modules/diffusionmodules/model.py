@@ -31,6 +31,7 @@ class Upsample(nn.Module):
         assert with_conv
         self.conv = H.Conv2d(in_channels, in_channels, 3, padding=1)
         self.conv.emit_colstats = True            # feeds the next ResnetBlock's GroupNorm
+        self.conv.upsamples = True                # prepare() builds its phase layout (Conv2d.packed_up4)
 
     def forward(self, x):
         return self.conv(x, upsample=True)

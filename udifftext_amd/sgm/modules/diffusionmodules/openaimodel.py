@@ -52,6 +52,7 @@ class Upsample(nn.Module):
         self.out_channels = out_channels or channels
         self.conv = H.Conv2d(channels, self.out_channels, 3, padding=padding)
         self.conv.emit_colstats = True            # feeds the next ResBlock's GroupNorm
+        self.conv.upsamples = True                # prepare() builds its phase layout (Conv2d.packed_up4)
 
     def forward(self, x):
         assert x.shape[-1] == self.channels

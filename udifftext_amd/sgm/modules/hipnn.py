@@ -260,6 +260,10 @@ class Conv2d(_Packed):
     def packed(self):
         return layout(self, "plain", self._pack, self.segments, self.n_pad)
 
+    def packed_up4(self):
+        """the phase layout (packing.pack_conv_up4) of a 3x3 convolution that reads its input through a nearest x2 upsample"""
+        return layout(self, "up4", lambda: packing.pack_conv_up4(self.weight, self.n_pad), self.n_pad)
+
     def forward(self, x, x2=None, residual=None, rowvec=None, upsample: bool = False, flags: int = 0,
                 pad: Optional[tuple] = None, out_hw: Optional[tuple] = None, norm: Optional["GroupNorm"] = None,
                 norm_silu: bool = False, colstats: Optional[bool] = None):
@@ -283,6 +287,10 @@ class Conv2d(_Packed):
         colstats = bool(colstats)
         kw = dict(ksize=self.kernel_size, stride=self.stride, pad=pad, upsample=upsample, out_hw=out_hw, residual=residual,
                   rowvec=rowvec, flags=flags, n_out=w.shape[0], colstats=colstats)
+        if upsample and norm is None and x2 is None and self.kernel_size == 3 and self.stride == 1:
+            # four 2x2 phase convolutions of the low-resolution map on pre-summed weights wherever the library serves the shape
+            # (ops.conv2d asks udt_gemm_up4_ok; otherwise the nine-tap launch on `w`)
+            kw["w_up4"] = self.packed_up4()
         in_scsh = None
         if norm is not None:
             st1, st2 = ops.gn_stats_of(x), ops.gn_stats_of(x2)
