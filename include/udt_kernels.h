@@ -28,7 +28,7 @@
  *                                               sgm/modules/diffusionmodules/openaimodel.py:183-187,218-221,536-538
  *                       GroupNorm(eps 1e-6)     sgm/modules/attention.py:82-85,402 ; model.py:48-52,128-143
  *   udt_layernorm       nn.LayerNorm            sgm/modules/attention.py:297,310-311,315-339
- *   udt_unet_input / udt_cfg_euler_step
+ *   udt_unet_input / udt_unet_input_churn / udt_cfg_euler_step
  *                       guider.prepare_inputs + denoiser scaling + CFG + Euler update
  *                       sgm/modules/diffusionmodules/guiders.py:25-40, denoiser.py:22-28,
  *                       denoiser_scaling.py:16-22, sampling_utils.py:8-9,39-40, sampling.py:85-86,348-351
@@ -387,6 +387,11 @@ int udt_layernorm(const void* x, void* y, const float* gamma, const float* beta,
 /* UNet input for one CFG step: x fp32 NCHW [B,4,h,w] -> xin bf16 NHWC [2B, h*w, cpad]; channels 0..3 of
  * both halves = x * c_in; the other channels (mask / masked latent / zero pad) are left untouched. */
 int udt_unet_input(const float* x, void* xin, int32_t B, int32_t hw, int32_t cpad, float c_in, void* stream);
+/* udt_unet_input of a churned (stochastic) Euler step, one launch: x <- x + kn*noise in place (noise fp32 NCHW [B,4,h,w], not
+ * x itself; kn = s_noise*sigma*sqrt(gamma^2 + 2*gamma) from the host), then channels 0..3 of both halves = the STORED x * c_in,
+ * bit-equal to udt_unet_input on the updated x.  B*hw <= 0x7fffffff. */
+int udt_unet_input_churn(float* x, const float* noise, void* xin, int32_t B, int32_t hw, int32_t cpad, float c_in, float kn,
+                         void* stream);
 /* eps fp32 [2B, hw, ld_eps] (uncond half first) -> x fp32 NCHW [B,4,h,w] updated in place:
  *   den_u = x + c_out*eps_u ; den_c = x + c_out*eps_c (c_out = -quantised sigma) ; den = den_u + scale*(den_c - den_u)
  *   d = (x - den)/sigma ; x += d*(sigma_next - sigma)          (optionally writes den) */

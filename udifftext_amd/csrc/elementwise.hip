@@ -1,5 +1,6 @@
 // elementwise.hip — sampler-step math and layout changes at the NCHW fp32 plugin boundary (HBM-bound).
 //
+//   udt_unet_input_churn                : sampling.py:328-331 (x += kn*noise) folded into udt_unet_input's launch
 //   udt_unet_input / udt_cfg_euler_step : guiders.py:25-40, denoiser.py:22-28, denoiser_scaling.py:16-22,
 //                                         sampling_utils.py:8-9,39-40, sampling.py:85-86,348-351
 //   udt_cfg_sampler_step                : the same CFG denoise + the update of any sampler of sampling.py:140-215,423-567
@@ -14,15 +15,30 @@
 
 namespace {
 
-__global__ void unet_input_kernel(const float* __restrict__ x, uint16_t* __restrict__ xin, int B, int hw, int cpad,
-                                  float c_in) {
+// CHURN: x <- x + kn*noise first (the stochastic Euler step's pre-evaluation noise, sampling.py:328-331), written back in place;
+// the packed value is c_in times the STORED x, so a later plain udt_unet_input on x writes the same bits.
+template <bool CHURN>
+__global__ void unet_input_kernel(float* __restrict__ x, const float* __restrict__ noise, uint16_t* __restrict__ xin, int B, int hw,
+                                  int cpad, float c_in, float kn) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;   // (b, pixel)
   if (i >= B * hw) return;
   const int b = i / hw;
   const int pix = i - b * hw;
-  const float* xb = x + (long long)b * 4 * hw + pix;
-  const float v0 = xb[0] * c_in, v1 = xb[hw] * c_in, v2 = xb[2 * hw] * c_in, v3 = xb[3 * hw] * c_in;
-  const u32x2 pk = {pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
+  float* xb = x + (long long)b * 4 * hw + pix;
+  float v[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) v[c] = xb[c * hw];
+  if (CHURN) {
+    const float* nb = noise + (long long)b * 4 * hw + pix;
+    float n[4];                                          // every load of the thread before the first store to x
+#pragma unroll
+    for (int c = 0; c < 4; ++c) n[c] = nb[c * hw];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) xb[c * hw] = v[c] = v[c] + kn * n[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) v[c] *= c_in;
+  const u32x2 pk = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
   *reinterpret_cast<u32x2*>(xin + ((long long)b * hw + pix) * cpad) = pk;
   *reinterpret_cast<u32x2*>(xin + ((long long)(b + B) * hw + pix) * cpad) = pk;
 }
@@ -310,8 +326,20 @@ extern "C" int udt_unet_input(const float* x, void* xin, int32_t B, int32_t hw, 
   if (!x || !xin) return UDT_ERR_BAD_ARG;
   if (B <= 0 || hw <= 0 || cpad < 8 || cpad % 8 != 0) return UDT_ERR_BAD_SHAPE;
   UDT_STREAM;
-  hipLaunchKernelGGL(unet_input_kernel, dim3(nblk((long long)B * hw)), dim3(256), 0, s, x,
-                     reinterpret_cast<uint16_t*>(xin), B, hw, cpad, c_in);
+  hipLaunchKernelGGL(unet_input_kernel<false>, dim3(nblk((long long)B * hw)), dim3(256), 0, s, const_cast<float*>(x),
+                     static_cast<const float*>(nullptr), reinterpret_cast<uint16_t*>(xin), B, hw, cpad, c_in, 0.f);
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}
+
+extern "C" int udt_unet_input_churn(float* x, const float* noise, void* xin, int32_t B, int32_t hw, int32_t cpad,
+                                    float c_in, float kn, void* stream) {
+  if (!x || !noise || !xin) return UDT_ERR_BAD_ARG;
+  if (noise == x) return UDT_ERR_BAD_ARG;
+  if (B <= 0 || hw <= 0 || cpad < 8 || cpad % 8 != 0 || (long long)B * hw > 0x7fffffffLL) return UDT_ERR_BAD_SHAPE;
+  UDT_STREAM;
+  hipLaunchKernelGGL(unet_input_kernel<true>, dim3(nblk((long long)B * hw)), dim3(256), 0, s, x, noise,
+                     reinterpret_cast<uint16_t*>(xin), B, hw, cpad, c_in, kn);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
 }

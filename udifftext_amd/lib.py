@@ -113,6 +113,7 @@ SYMBOLS = {
     "udt_gn_strip": (C.c_int, [_vp, _vp, _vp, _fp, _fp, _i32, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
     "udt_layernorm": (C.c_int, [_vp, _vp, _fp, _fp, _i64, _i32, _f32, _vp]),
     "udt_unet_input": (C.c_int, [_fp, _vp, _i32, _i32, _i32, _f32, _vp]),
+    "udt_unet_input_churn": (C.c_int, [_fp, _fp, _vp, _i32, _i32, _i32, _f32, _f32, _vp]),
     "udt_cfg_euler_step": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
     "udt_cfg_sampler_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, SamplerCoefs, _vp]),
     "udt_cfg_multistep_step": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, MultistepCoefs, _vp]),

@@ -759,6 +759,16 @@ def unet_input(x: torch.Tensor, xin: torch.Tensor, c_in: float) -> None:
     L.check(L.load().udt_unet_input(_ptr(x), _ptr(xin), B, h * w, xin.shape[-1], c_in, _stream()), "udt_unet_input")
 
 
+def unet_input_churn(x: torch.Tensor, noise: torch.Tensor, xin: torch.Tensor, c_in: float, kn: float) -> None:
+    """one launch of udt_unet_input_churn: x <- x + kn*noise in place (x, noise: fp32 NCHW [B,4,h,w] contiguous, distinct), then
+    unet_input on the stored x"""
+    B, _, h, w = x.shape
+    for t in (x, noise):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, 4, h, w), "fp32 NCHW [B,4,h,w]"
+    L.check(L.load().udt_unet_input_churn(_ptr(x), _ptr(noise), _ptr(xin), B, h * w, xin.shape[-1], c_in, kn, _stream()),
+            "udt_unet_input_churn")
+
+
 def cfg_euler_step(x: torch.Tensor, eps: torch.Tensor, sigma: float, sigma_next: float, scale: float,
                    denoised: Optional[torch.Tensor] = None, c_out: Optional[float] = None) -> None:
     """c_out defaults to -sigma (EpsScaling); pass the quantised value when it differs from sigma."""

@@ -48,10 +48,12 @@ SAMPLERS = {
 }
 
 
-def init_sampling(steps: int, scale: float, device: torch.device, verbose: bool = False, sampler: str = "euler"):
+def init_sampling(steps: int, scale: float, device: torch.device, verbose: bool = False, sampler: str = "euler", *,
+                  s_churn: float = 0.0, s_tmin: float = 0.0, s_tmax: float = 999.0, s_noise: float = 1.0):
     """reference util.py:24-47: EulerEDMSampler + LegacyDDPMDiscretization + VanillaCFG(scale).  ``sampler`` picks another
     sampler of the reference's sampling.py with the same discretization and guider (SAMPLERS; their default parameters:
-    eta = s_noise = 1 for the ancestral ones, s_churn = 0 for Heun, order = 4 for linear_multistep)"""
+    eta = s_noise = 1 for the ancestral ones, order = 4 for linear_multistep).  ``s_churn`` / ``s_tmin`` / ``s_tmax`` / ``s_noise``
+    (the Karras churn settings, reference sampling.py:89-98) go to "euler" and "heun"; Euler runs s_churn > 0, Heun refuses it"""
     from sgm.modules.diffusionmodules import sampling as S
     if sampler not in SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}; one of {sorted(SAMPLERS)}")
@@ -61,7 +63,7 @@ def init_sampling(steps: int, scale: float, device: torch.device, verbose: bool 
         guider_config={"target": "sgm.modules.diffusionmodules.guiders.VanillaCFG", "params": {"scale": scale}},
         verbose=verbose, device=device)
     if sampler in ("euler", "heun"):
-        common.update(s_churn=0.0, s_tmin=0.0, s_tmax=999.0, s_noise=1.0)
+        common.update(s_churn=s_churn, s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise)
     return getattr(S, SAMPLERS[sampler])(**common)
 
 
@@ -211,7 +213,7 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
                     c, uc = model.conditioner.get_unconditional_conditioning(
                         b, batch_uc=buc, force_uc_zero_embeddings=cfgs.force_uc_zero_embeddings)
                     xs.append(sampler.get_init_noise(cfgs, model, cond=c, batch=b, uc=uc))
-                    if draw_noise is not None:      # ancestral samplers: the run's step noise, right after the initial noise
+                    if draw_noise is not None:      # ancestral / churned samplers: the run's step noise, right after the initial noise
                         noises.append(draw_noise(xs[-1].shape, xs[-1].device, None, cfgs.init_step))
                 cs.append(c)
                 ucs.append(uc)

@@ -1,5 +1,6 @@
 """Samplers.  ``EulerEDMSampler`` is the one UDiffText instantiates (reference util.py:35-45); with s_churn = 0 it
-is the deterministic Euler == DDIM(eta 0) integrator with classifier-free guidance.
+is the deterministic Euler == DDIM(eta 0) integrator with classifier-free guidance, with s_churn > 0 the stochastic
+(Karras "churn") one: udt_unet_input_churn adds the step's noise in the launch that packs the UNet input.
 
 Reference: sgm/modules/diffusionmodules/sampling.py — BaseDiffusionSampler :28-78, EDMSampler :89-98,
 EulerEDMSampler :218-420 (get_init_noise :264-322, sampler_step :324-353, __call__ :355-420).
@@ -129,9 +130,10 @@ def _is_capture_failure(e: BaseException) -> bool:
 
 class EulerEval(NamedTuple):
     """one UNet evaluation + the in-place Euler update of src from sigma to sigma_next (udt_cfg_euler_step: _Stepper.step)"""
-    sigma: float
+    sigma: float                       # sigma_hat = sigma_i*(1 + gamma_i) on a churned step, else sigma_i (unquantised)
     sigma_next: float
     src: str = "x"
+    churn: float = 0.0                 # != 0: src += churn * noise[slot] before the evaluation (udt_unet_input_churn)
 
 
 class Eval(NamedTuple):
@@ -148,6 +150,7 @@ class Eval(NamedTuple):
     kp: float = 0.0
     kn: float = 0.0
     den_out: Optional[str] = None
+    churn: float = 0.0                 # as EulerEval.churn (set by no sampler yet: Heun churn would be a plan change only)
 
 
 class MultistepEval(NamedTuple):
@@ -176,9 +179,24 @@ def plan_buffers(plans) -> list:
     return names
 
 
+def _churn(e) -> float:
+    return e.churn if isinstance(e, (EulerEval, Eval)) else 0.0
+
+
+def plan_noise_slots(plans) -> Dict[int, int]:
+    """step index -> slot of the run's noise buffer (draw_step_noise).  Ancestral plans (an ``Eval`` with kn != 0): one draw per
+    step of ``plans``, the last step included, slot = position.  Churned plans (an evaluation with churn != 0): one draw per
+    CHURNED step, the k-th churned step reads slot k; the other steps draw nothing and have no slot."""
+    if any(isinstance(e, Eval) and e.kn != 0.0 for _, plan in plans for e in plan):
+        return {i: k for k, (i, _) in enumerate(plans)}
+    churned = [i for i, plan in plans if any(_churn(e) != 0.0 for e in plan)]
+    return {i: k for k, i in enumerate(churned)}
+
+
 def plans_add_noise(plans) -> bool:
-    """does an evaluation of ``plans`` add the step's ancestral draw?"""
-    return any(isinstance(e, Eval) and e.kn != 0.0 for _, plan in plans for e in plan)
+    """does an evaluation of ``plans`` read a draw (ancestral noise after the update, or churn before the evaluation)?"""
+    return bool(plan_noise_slots(plans))
+
 
 class _Stepper:
     """Step-invariant device state of one sampling run + the fused per-step launch sequence."""
@@ -234,12 +252,18 @@ class _Stepper:
             self._emb_cache[idx] = rows
         return rows
 
-    def unet_eps(self, x: torch.Tensor, sigma: float, emit_maps: bool = False):
+    def unet_eps(self, x: torch.Tensor, sigma: float, emit_maps: bool = False, churn: float = 0.0,
+                 noise: Optional[torch.Tensor] = None):
         """the CFG pair's UNet call on x (fp32 NCHW [B,4,h,w]) at the quantised sigma -> (eps fp32 NHWC [2B,h,w,ld],
-        quantised sigma)"""
+        quantised sigma); churn != 0: x += churn * noise first, in the same launch that packs the UNet input"""
         idx, sq = self.quantise(sigma)
         c_in = 1.0 / (sq * sq + 1.0) ** 0.5
-        ops.unet_input(x, self.xin, c_in)
+        if churn != 0.0:
+            if noise is None:
+                raise ValueError("a churned evaluation needs the step's draw (draw_step_noise)")
+            ops.unet_input_churn(x, noise, self.xin, c_in, churn)
+        else:
+            ops.unet_input(x, self.xin, c_in)
         if emit_maps:
             self.unet.clear_attn_map()
         emb = self.emb_rows(idx)
@@ -252,25 +276,27 @@ class _Stepper:
         return eps, sq
 
     def step(self, x: torch.Tensor, sigma: float, sigma_next: float, emit_maps: bool = False,
-             denoised: Optional[torch.Tensor] = None) -> None:
-        """in-place Euler update of x (fp32 NCHW [B,4,h,w]); denoised (optional): receives the guided denoised latent"""
-        eps, sq = self.unet_eps(x, sigma, emit_maps)
+             denoised: Optional[torch.Tensor] = None, churn: float = 0.0, noise: Optional[torch.Tensor] = None) -> None:
+        """in-place Euler update of x (fp32 NCHW [B,4,h,w]) from sigma (sigma_hat on a churned step: x += churn * noise before
+        the evaluation) to sigma_next; denoised (optional): receives the guided denoised latent"""
+        eps, sq = self.unet_eps(x, sigma, emit_maps, churn, noise)
         ops.cfg_euler_step(x, eps, sigma, sigma_next, self.scale, denoised=denoised, c_out=-sq)
 
     def run_plan(self, bufs: Dict[str, torch.Tensor], plan, noise: Optional[torch.Tensor] = None) -> None:
         """one sampler step: per evaluation of ``plan`` (a tuple of ``EulerEval`` / ``Eval`` / ``MultistepEval``), the UNet call
         on its source buffer and its fused launch; ``bufs`` maps the plan's buffer names to fp32 NCHW tensors, ``noise`` is this
-        step's ancestral draw"""
+        step's draw (ancestral or churn: plan_noise_slots)"""
         for e in plan:
             src = bufs[e.src]
             if isinstance(e, EulerEval):
-                self.step(src, e.sigma, e.sigma_next)
+                self.step(src, e.sigma, e.sigma_next, churn=e.churn, noise=noise)
                 continue
-            eps, sq = self.unet_eps(src, e.sigma)
             if isinstance(e, MultistepEval):
+                eps, sq = self.unet_eps(src, e.sigma)
                 ops.cfg_multistep_step(src, eps, -sq, self.scale, e.sigma, (e.k0,) + tuple(k for _, k in e.hist),
                                        hist=[bufs[b] for b, _ in e.hist], d_out=bufs[e.d_out], out=bufs[e.out])
                 continue
+            eps, sq = self.unet_eps(src, e.sigma, churn=e.churn, noise=noise)
             ops.cfg_sampler_step(src, eps, -sq, self.scale, e.kx, e.kd,
                                  aux=bufs[e.aux] if e.aux else None, ka=e.ka,
                                  prev=bufs[e.prev] if e.prev else None, kp=e.kp,
@@ -307,8 +333,9 @@ class _GraphedSteps:
     replayed for every later batch of the same shape: the host then issues 50 graph launches per batch instead of
     ~29,000 kernel launches (8 ms of Python / ctypes time per step), and the command processor walks the kernels
     back to back.  Conditioning (text k|v projections, concat channels) lives in static device buffers that
-    ``rebind`` refreshes in place; the latent ``x``, the scratch / history buffers the plans name and, if a plan adds
-    noise, the run's ancestral draws ([steps, B, 4, h, w], refreshed per run by ``load``) are static fp32 buffers.
+    ``rebind`` refreshes in place; the latent ``x``, the scratch / history buffers the plans name and, if a plan reads
+    noise, the run's draws ([slots, B, 4, h, w] — one per step for ancestral plans, one per churned step for churned ones,
+    plan_noise_slots — refreshed per run by ``load``) are static fp32 buffers; each captured step has its slot baked in.
     A runner serves one sequence of ``plans`` ((step, plan) pairs; by default Euler over every step of ``sig``), one
     graph per step index."""
 
@@ -327,8 +354,9 @@ class _GraphedSteps:
         self.bufs = {"x": self.x}
         for name in plan_buffers(plans):                  # e.g. LinearMultistepSampler's derivative ring d0 .. d{order-1}
             self.bufs[name] = torch.zeros_like(self.x)
-        self.noise = (torch.zeros((len(plans),) + tuple(self.x.shape), dtype=torch.float32, device=self.st.dev)
-                      if plans_add_noise(plans) else None)
+        self.slots = plan_noise_slots(plans)
+        self.noise = (torch.zeros((len(self.slots),) + tuple(self.x.shape), dtype=torch.float32, device=self.st.dev)
+                      if self.slots else None)
         self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self.pool = torch.cuda.graph_pool_handle()
         self.capture_stream = torch.cuda.Stream(device=self.st.dev)
@@ -351,14 +379,14 @@ class _GraphedSteps:
         return True
 
     def load(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None) -> None:
-        """the run's latent and, if a plan adds noise, its ancestral draws (draw_step_noise)"""
+        """the run's latent and, if a plan reads noise, its draws (draw_step_noise)"""
         self.x.copy_(x)
         if self.noise is not None and noise is not None:
             self.noise.copy_(noise)
 
     def _capture(self, i: int) -> torch.cuda.CUDAGraph:
         st, plan = self.st, self.plans[i]
-        noise = self.noise[list(self.plans).index(i)] if self.noise is not None else None
+        noise = self.noise[self.slots[i]] if i in self.slots else None
         for e in plan:
             st.emb_rows(st.quantise(e.sigma)[0])             # time-embedding rows are cached outside the graph
         if not self.warm:
@@ -408,6 +436,7 @@ class _PlanSampler:
     flight (``sample_in_flight``) — and draws the initial noise (the noise search does not depend on the sampler)"""
     use_graphs = os.environ.get("UDT_GRAPHS", "1") != "0"      # hipGraph replay of the main loop (eager launches if off)
     uses_noise = False                 # ancestral samplers: one rng draw [B,4,h,w] per step, the last step included
+    implements_churn = False           # s_churn > 0 (EDMSampler): EulerEDMSampler only
 
     def step_plan(self, sig, i: int, init_step: int = 0) -> tuple:
         """the evaluations of step i (sig: host sigmas, len num_steps + 1) -> tuple of EulerEval / Eval / MultistepEval"""
@@ -423,24 +452,29 @@ class _PlanSampler:
     def _check_fast_path(self):
         if not isinstance(self.guider, VanillaCFG):
             raise NotImplementedError("the fused MI355X step implements VanillaCFG guidance")
-        if getattr(self, "s_churn", 0.0) != 0.0:
-            raise NotImplementedError("s_churn > 0 (stochastic sampling) is not implemented by the fused samplers "
-                                      "(UDiffText uses 0, util.py:39)")
+        if getattr(self, "s_churn", 0.0) != 0.0 and not self.implements_churn:
+            raise NotImplementedError(f"s_churn > 0 (stochastic sampling) is implemented for EulerEDMSampler only, not "
+                                      f"{type(self).__name__}")
 
     def draw_step_noise(self, shape, device, num_steps=None, init_step: int = 0) -> Optional[torch.Tensor]:
         """the ancestral draws of one run: one rng.randn of ``shape`` per step from init_step on, in step order, as ONE device
-        buffer [steps, *shape] (None for the deterministic samplers).  Drawn up front so that graph replays can read a slice
-        per step; the values equal per-step draws because the CPU streams are sequential."""
+        buffer [steps, *shape] (None for the deterministic samplers; EulerEDMSampler: one per churned step).  Drawn up front so
+        that graph replays can read a slice per step; the values equal per-step draws because the CPU streams are sequential."""
         if not self.uses_noise:
             return None
         n = len(self._host_sigmas(num_steps)) - 1 - init_step
         return rng.randn_steps_on(n, shape, device)
 
     # -------------------------------------------------------------------------------------- noise search
+    def _search_plans(self, sig):
+        """the noise search's two steps: plain Euler under every sampler (EulerEDMSampler: its own, possibly churned, steps)"""
+        return [(i, (EulerEval(sig[i], sig[i + 1]),)) for i in range(len(sig) - 1)]
+
     def get_init_noise(self, cfgs, model, cond, batch, uc=None):
         """noise_iters candidates, each scored by the text-attention local loss after the 2nd of 2 Euler steps;
         the per-sample arg-min is kept (identical to the reference for batch 1; the reference is undefined for
-        larger batches).  All randn draws come from the CPU default generator, in the reference's order."""
+        larger batches).  All randn draws come from the CPU default generator, in the reference's order (churn draws of
+        EulerEDMSampler(s_churn > 0) included: the order of the reference run on the CPU)."""
         self._check_fast_path()
         H, W = batch["target_size_as_tuple"][0]
         shape = (cfgs.batch_size, cfgs.channel, int(H) // cfgs.factor, int(W) // cfgs.factor)
@@ -449,13 +483,20 @@ class _PlanSampler:
         if cfgs.noise_iters <= 0:
             return randn
         sig = self._host_sigmas(2)
+        plans = self._search_plans(sig)
+        slots = plan_noise_slots(plans)
         mask, seg = batch["mask"], batch["seg_mask"]
         B, K = shape[0], int(cfgs.noise_iters)
         uc = default(uc, cond)
         # the reference draws the first candidate, then one more after scoring each (the last draw is never used but advances the
-        # generator): K + 1 draws in the same order
-        cands = [randn] + [rng.randn_on(shape, dev) for _ in range(K)]
-        cands, scores = cands[:K], []
+        # generator): K + 1 draws in the same order.  Under churn every scored candidate's steps draw too (the reference run on
+        # the CPU): candidate k, its churn draws in step order, candidate k + 1, ..., the unused last candidate — all taken here,
+        # up front, in that order
+        cands, churn, scores = [randn], [], []
+        for _ in range(K):
+            churn.append(rng.randn_steps_on(len(slots), shape, dev) if slots else None)
+            cands.append(rng.randn_on(shape, dev))
+        cands = cands[:K]
         # candidates are independent of each other (2 Euler steps + the local loss of THAT candidate's attention maps), so they
         # run as extra batch entries of the same UNet calls: up to 16 samples (32 with the CFG pair) per call instead of K
         # sequential 2-step runs on B samples — the reference-default workload (batch 1, noise_iters 10) is launch-latency-bound
@@ -472,8 +513,9 @@ class _PlanSampler:
             x = torch.cat(chunk, 0).clone()
             x *= (1.0 + sig[0] ** 2.0) ** 0.5
             ll = None
-            for i in range(2):
-                stepper.step(x, sig[i], sig[i + 1], emit_maps=True)
+            for i, (e,) in plans:
+                nz = torch.cat([c[slots[i]] for c in churn[g0:g0 + G]], 0) if i in slots else None
+                stepper.step(x, e.sigma, e.sigma_next, emit_maps=True, churn=e.churn, noise=nz)
                 ll = model.loss_fn.get_min_local_loss(stepper.unet.attn_map_cache, mask, seg, cond_only=True)
             scores.extend(ll.reshape(g, B).unbind(0))
             stepper.unet.clear_attn_map()
@@ -514,8 +556,9 @@ class _PlanSampler:
         bufs = {"x": x}
         for name in plan_buffers(plans):
             bufs[name] = torch.empty_like(x)
+        slots = plan_noise_slots(plans)
         for i, plan in plans:
-            stepper.run_plan(bufs, plan, noise[i - init_step] if noise is not None else None)
+            stepper.run_plan(bufs, plan, noise[slots[i]] if noise is not None and i in slots else None)
         stepper.check()
         return x
 
@@ -674,7 +717,30 @@ AAE_GRAPH = os.environ.get("UDT_AAE_GRAPH", "1") != "0"      # hipGraph replay o
 
 class EulerEDMSampler(_PlanSampler, EDMSampler):
     """reference sampling.py:218-420: one udt_cfg_euler_step evaluation per step (``EulerEval``) through the shared loop; the
-    attend-and-excite loop, the reference-shaped ``sampler_step`` and the ``detailed`` attention-map dump are its own"""
+    attend-and-excite loop, the reference-shaped ``sampler_step`` and the ``detailed`` attention-map dump are its own.
+
+    s_churn > 0 (reference :89-137, :324-353): step i of n = num_sigmas - 1 has gamma_i = min(s_churn / n, sqrt(2) - 1) where
+    s_tmin <= sigma_i <= s_tmax, else 0 (init_step does not change n).  A churned step first raises the noise level to
+    sigma_hat = sigma_i (1 + gamma_i), x += s_noise sqrt(sigma_hat^2 - sigma_i^2) eps, then evaluates and steps from sigma_hat;
+    the noise lands in the launch that packs the UNet input (udt_unet_input_churn), so the step's launch count is unchanged.
+    One rng draw per churned step, in step order (``draw_step_noise``); gamma_i = 0 is exactly the deterministic step."""
+    implements_churn = True
+
+    def churn_gamma(self, sig, i: int) -> float:
+        """reference :122-126: gamma of step i of the host schedule ``sig``"""
+        return min(self.s_churn / (len(sig) - 1), 2 ** 0.5 - 1) if self.s_tmin <= sig[i] <= self.s_tmax else 0.0
+
+    def draw_step_noise(self, shape, device, num_steps=None, init_step: int = 0) -> Optional[torch.Tensor]:
+        """the churn draws of one run: one rng.randn of ``shape`` per CHURNED step from init_step on, in step order, as one buffer
+        [n_churned, *shape] (the k-th churned step reads slot k); None, and no generator advances, when no step is churned"""
+        if not self.s_churn:
+            return None
+        sig = self._host_sigmas(num_steps)
+        n = sum(1 for i in range(init_step, len(sig) - 1) if self.step_plan(sig, i, init_step)[0].churn != 0.0)
+        return rng.randn_steps_on(n, shape, device) if n else None
+
+    def _search_plans(self, sig):
+        return [(i, self.step_plan(sig, i)) for i in range(len(sig) - 1)]
 
     def possible_correction_step(self, euler_step, x, d, dt, next_sigma, denoiser, cond, uc):
         return euler_step
@@ -729,8 +795,11 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
                      thres=None, update=False, name=None, save_loss=False, save_attn=False, save_inter=False):
         """reference-shaped single step on tensors (sigma / next_sigma are [B] tensors); returns
         (x_next, denoised_decode, local_loss).  Generic formulation via denoiser + guider."""
-        if gamma > 0:
-            raise NotImplementedError("s_churn > 0 (stochastic sampling) is not used by UDiffText (util.py:39)")
+        if gamma > 0:                                                      # reference :328-331, eps from the path's noise source
+            sigma_hat = sigma * (gamma + 1.0)
+            eps = rng.randn_on(x.shape, x.device).to(x.dtype) * self.s_noise
+            x = x + eps * ((sigma_hat ** 2 - sigma ** 2) ** 0.5)[(...,) + (None,) * (x.ndim - 1)]
+            sigma = sigma_hat
         if update:
             x = self.attend_and_excite(x, model, sigma, cond, batch, alpha, iter_enabled, thres)
         denoised = self.denoise(x, model, sigma, cond, uc)
@@ -757,17 +826,27 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
 
     # ------------------------------------------------------------------------------------------- loop
     def step_plan(self, sig, i, init_step=0):
-        return (EulerEval(sig[i], sig[i + 1]),)
+        gamma = self.churn_gamma(sig, i) if self.s_churn else 0.0
+        if gamma == 0.0:
+            return (EulerEval(sig[i], sig[i + 1]),)
+        s = float(sig[i])
+        # s_noise sqrt(sigma_hat^2 - sigma^2) without the cancellation, in float64 (a negative gamma lowers sigma_hat and adds
+        # nothing, like the reference's ``if gamma > 0``)
+        kn = self.s_noise * s * (gamma * gamma + 2.0 * gamma) ** 0.5 if gamma > 0 else 0.0
+        return (EulerEval(s * (1.0 + gamma), sig[i + 1], churn=kn),)
 
     def __call__(self, model, x, cond, batch=None, uc=None, num_steps=None, init_step=0, name=None, aae_enabled=False,
-                 detailed=False):
+                 detailed=False, noise: Optional[torch.Tensor] = None):
+        """``noise``: the run's churn draws (draw_step_noise), drawn here when not given"""
         if not (aae_enabled or detailed):
-            return self._sample(model, x, cond, uc, num_steps, init_step)
+            return self._sample(model, x, cond, uc, num_steps, init_step, noise)
         self._check_fast_path()
         require_gpu(x, "EulerEDMSampler")
         uc = default(uc, cond)
+        if noise is None:
+            noise = self.draw_step_noise(x.shape, x.device, num_steps, init_step)
         if aae_enabled:
-            return self._sample_with_attend_and_excite(model, x, cond, batch, uc, num_steps, init_step, name, detailed)
+            return self._sample_with_attend_and_excite(model, x, cond, batch, uc, num_steps, init_step, name, detailed, noise)
         # reference sampling.py:384,344-346: at the middle step the text cross-attention maps of the configured layers are plotted
         # and the label's per-character maps saved.  That one step runs with map emission (eager launches, the xattn chain); every
         # other step is the fast step — the loop is the same Euler loop, so the latent equals the plain call's up to the two
@@ -778,19 +857,23 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         name = name if name is not None else (batch["name"][0] if batch is not None and "name" in batch else "sample")
         stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale)
         mid = (len(sig) - 1) // 2
+        slot = 0                                                           # the k-th churned step reads draw k
         for i in self.get_sigma_gen(len(sig), init_step=init_step):
-            stepper.step(x, sig[i], sig[i + 1], emit_maps=(i == mid))
+            (e,) = self.step_plan(sig, i, init_step)
+            stepper.step(x, e.sigma, e.sigma_next, emit_maps=(i == mid), churn=e.churn, noise=noise[slot] if e.churn != 0.0 else None)
+            slot += e.churn != 0.0
             if i == mid:
                 attn_map = stepper.unet.save_attn_map(save_name=name, tokens=batch["label"][0])
                 self.save_segment_map(attn_map, tokens=batch["label"][0], save_name=name)
         stepper.check()
         return x
 
-    def _sample_with_attend_and_excite(self, model, x, cond, batch, uc, num_steps, init_step, name, detailed):
+    def _sample_with_attend_and_excite(self, model, x, cond, batch, uc, num_steps, init_step, name, detailed, noise=None):
         """reference sampling.py:355-420 with aae_enabled: before every denoising step the latent takes attend-and-excite updates
         (alpha = 20 sqrt(scale_i); iterated at steps 5, 9, ..., 25 down to thresholds -0.5 ... -0.8), the local loss of every step
         is collected and every intermediate denoised latent decoded (the reference writes them as a GIF; imageio is optional
-        here).  Eager launches: the update's step count is data-dependent."""
+        here).  Eager launches: the update's step count is data-dependent.  A churned step adds its noise BEFORE the update, and
+        the update and the step run at sigma_hat (reference :328-336)."""
         import numpy as np
         sig = self._host_sigmas(num_steps)
         num_sigmas = len(sig)
@@ -806,13 +889,18 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         evals0 = getattr(self, "aae_evaluations", 0)
         inters, local_losses = [], []
         mid = (num_sigmas - 1) // 2
+        slot = 0                                                           # the k-th churned step reads draw k
         for i in self.get_sigma_gen(num_sigmas, init_step=init_step):
+            (e,) = self.step_plan(sig, i, init_step)
             alpha = 20 * np.sqrt(scales[i])
             iter_enabled = i in iter_lst
             thres = float(thres_lst[list(iter_lst).index(i)]) if iter_enabled else 0.0
-            x = self.attend_and_excite(x, model, s_in * sig[i], cond, batch, alpha, iter_enabled, thres)
+            if e.churn != 0.0:
+                ops.axpy_(x, noise[slot], e.churn)
+                slot += 1
+            x = self.attend_and_excite(x, model, s_in * e.sigma, cond, batch, alpha, iter_enabled, thres)
             den = torch.empty_like(x)
-            stepper.step(x, sig[i], sig[i + 1], emit_maps=True, denoised=den)
+            stepper.step(x, e.sigma, e.sigma_next, emit_maps=True, denoised=den)
             ll = model.loss_fn.get_min_local_loss(stepper.unet.attn_map_cache, batch["mask"], batch["seg_mask"], cond_only=True)
             local_losses.append(float(ll.mean()))
             if detailed and i == mid:
