@@ -299,9 +299,9 @@ __global__ void add_bf16_kernel(uint16_t* __restrict__ x, const uint16_t* __rest
   *reinterpret_cast<u32x4*>(x + i * 8) = a;
 }
 
-// out[r][c] = x[r][c] + bias[c]  (bf16 rows, fp32 bias, 8 channels per thread)
-__global__ void bias_add_kernel(const uint16_t* __restrict__ x, const float* __restrict__ bias, uint16_t* __restrict__ out,
-                                long long n8, int c8) {
+// out[r][c] = x[r][c] + bias[c]  (bf16 rows, fp32 bias, 8 channels per thread); x and out may be the same buffer (udt_kernels.h), so
+// neither is __restrict__
+__global__ void bias_add_kernel(const uint16_t* x, const float* __restrict__ bias, uint16_t* out, long long n8, int c8) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n8) return;
   const int c = (int)(i % c8) * 8;
