@@ -430,6 +430,30 @@ typedef struct {
 } udt_multistep_coefs;
 int udt_cfg_multistep_step(const float* xin, const float* eps, float* xout, float* d_out, int32_t B, int32_t hw,
                            int32_t ld_eps, udt_multistep_coefs k, void* stream);
+/* ---- the same four launches under any preconditioning (denoiser_scaling.py: Eps / V / EDM) and with or without guidance ----
+ * F is the network output, fp32 [2B, hw, ld_f] (uncond half first) when pair != 0 (VanillaCFG), fp32 [B, hw, ld_f] when pair == 0
+ * (IdentityGuider); 16-byte aligned, ld_f >= 4, ld_f % 4 == 0, B*hw <= 0x7fffffff.  c_skip, c_out, c_in are host floats (float64
+ * from the possibly quantised sigma, rounded once).
+ *   pair != 0: den_u = c_skip*x + c_out*F_u ; den_c = c_skip*x + c_out*F_c ; den = den_u + scale*(den_c - den_u)
+ *   pair == 0: den   = c_skip*x + c_out*F                                     (scale is not read)
+ * udt_cfg_euler_step / udt_cfg_sampler_step / udt_cfg_multistep_step are these with c_skip = 1, pair = 1, bit for bit. */
+/* UNet input: channels 0..3 of rows [0, B) of xin bf16 NHWC [(pair ? 2B : B), hw, cpad] = x * c_in, and of rows [B, 2B) as well when
+ * pair != 0; rows [B, 2B) are not written when pair == 0.  noise != NULL: the churned form, x <- x + kn*noise in place first
+ * (noise fp32 NCHW [B,4,h,w], not x itself), the packed value is the STORED x * c_in. */
+int udt_precond_unet_input(float* x, const float* noise, void* xin, int32_t B, int32_t hw, int32_t cpad, float c_in, float kn,
+                           int32_t pair, void* stream);
+/*   d = (x - den)/sigma ; x += d*(sigma_next - sigma)          (optionally writes den; den_out is not x) */
+int udt_precond_euler_step(float* x, const float* f, float* denoised_out, int32_t B, int32_t hw, int32_t ld_f, float c_skip,
+                           float c_out, float sigma, float sigma_next, float cfg_scale, int32_t pair, void* stream);
+/*   xout = kx*xin + kd*den + ka*aux + kp*prev + kn*noise     (a null pointer drops its term) ; den_out = den (optional)
+ * c_out and scale are k.c_out and k.scale; aliasing as udt_cfg_sampler_step. */
+int udt_precond_sampler_step(const float* xin, const float* f, const float* aux, const float* prev, const float* noise,
+                             float* xout, float* denoised_out, int32_t B, int32_t hw, int32_t ld_f, udt_sampler_coefs k,
+                             float c_skip, int32_t pair, void* stream);
+/*   d = (xin - den)/sigma ; xout = xin + (k[0]*d + k[1]*hist[1] + ... + k[n-1]*hist[n-1]) ; d_out = d
+ * c_out, scale and sigma are k.c_out, k.scale and k.sigma; aliasing as udt_cfg_multistep_step. */
+int udt_precond_multistep_step(const float* xin, const float* f, float* xout, float* d_out, int32_t B, int32_t hw, int32_t ld_f,
+                               udt_multistep_coefs k, float c_skip, int32_t pair, void* stream);
 /* z = scale * (mean + exp(0.5*clamp(logvar,-30,20)) * noise); moments fp32 [B, hw, ldm] NHWC (mean ch 0..3,
  * logvar ch 4..7), noise fp32 NCHW [B,4,h,w], z fp32 NCHW [B,4,h,w]. */
 int udt_posterior_sample(const float* moments, const float* noise, float* z, int32_t B, int32_t hw, int32_t ldm,
@@ -446,7 +470,8 @@ int udt_nhwc_set_channels(const float* src, void* dst, int32_t B, int32_t C, int
 /* out bf16 [n_tok, D] = table[idx[i]] + pe[i % L]  (table fp32 [V, D], pe fp32 [L, D], idx int32) */
 int udt_embed_tokens(const int32_t* idx, const float* table, const float* pe, void* out, int32_t n_tok, int32_t L,
                      int32_t D, void* stream);
-/* out bf16 [n, dim]: [cos(t f_k) | sin(t f_k)], f_k = exp(-ln(10000) k / (dim/2)); t int64-valued fp32 */
+/* out bf16 [n, dim]: [cos(t f_k) | sin(t f_k)], f_k = exp(-ln(10000) k / (dim/2)); t fp32, any real value (a timestep index or
+ * a continuous c_noise such as EDMScaling's 0.25 ln sigma) */
 int udt_timestep_embedding(const float* t, void* out, int32_t n, int32_t dim, void* stream);
 /* bilinear x1/8 (align_corners False) of fp32 [B,1,H,W] -> fp32 [B,1,H/8,W/8]: mean of the centre 2x2 */
 int udt_mask_downsample(const float* mask, float* out, int32_t B, int32_t H, int32_t W, void* stream);
@@ -559,6 +584,12 @@ int udt_local_loss_seg_bwd_hw(const float* probs, const float* seg, const float*
  * target)^2) and d_eps bf16 NHWC [B, hw, cpad] = d mean_b(loss_b) / d eps; eps fp32 NHWC [B, hw, ld_eps], noised / target fp32 NCHW */
 int udt_diff_loss_grad(const float* eps, const float* noised, const float* target, const float* sigma, void* d_eps, float* loss, int32_t B,
                        int32_t hw, int32_t ld_eps, int32_t cpad, void* stream);
+/* the same loss under any preconditioning / weighting, per-sample fp32 coefficients c_skip[B], c_out[B], w[B] (host values of
+ * denoiser.scaling / denoiser.w): out = c_skip_b*noised + c_out_b*F ; loss fp32 [B] = mean(w_b (out - target)^2) and
+ * d_f bf16 NHWC [B, hw, cpad] = d mean_b(loss_b) / d F = 2 w_b c_out_b (out - target) / (B * 4 hw); layout and reduction as
+ * udt_diff_loss_grad (which stays the eps path's launch) */
+int udt_precond_loss_grad(const float* f, const float* noised, const float* target, const float* c_skip, const float* c_out,
+                          const float* w, void* d_f, float* loss, int32_t B, int32_t hw, int32_t ld_f, int32_t cpad, void* stream);
 /* torch.optim.AdamW step on fp32 parameters (diffusion.py:49-51,219): g is scaled by grad_scale first (gradient accumulation / world) */
 int udt_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int32_t step, float grad_scale, void* stream);

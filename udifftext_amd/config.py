@@ -49,17 +49,36 @@ def _vae_config() -> dict:
                        "lossconfig": {"target": "torch.nn.Identity"}}}
 
 
-def default_model_config() -> AttrDict:
+_PAIRS = {"eps": ("EpsScaling", "EpsWeighting", False), "v": ("VScaling", "VWeighting", False),
+          "edm": ("EDMScaling", "EDMWeighting", True)}
+
+
+def denoiser_config(parameterization: str = "eps", discrete: bool = True, sigma_data: float = 0.5) -> dict:
+    """the ``denoiser_config`` of a model: DiscreteDenoiser (sigma quantised on the 1000-entry DDPM table) or the continuous
+    Denoiser, with the scaling / weighting pair of ``parameterization`` as the reference's configs pair them (Eps/Eps, V/V,
+    EDM/EDM; ``sigma_data`` goes to the EDM pair)"""
+    if parameterization not in _PAIRS:
+        raise ValueError(f"unknown parameterization {parameterization!r}; one of {sorted(_PAIRS)}")
+    scaling, weighting, takes_sd = _PAIRS[parameterization]
+    mod = "sgm.modules.diffusionmodules."
+    sc = {"target": f"{mod}denoiser_scaling.{scaling}"}
+    wt = {"target": f"{mod}denoiser_weighting.{weighting}"}
+    if takes_sd:
+        sc["params"] = {"sigma_data": sigma_data}
+        wt["params"] = {"sigma_data": sigma_data}
+    if discrete:
+        return {"target": f"{mod}denoiser.DiscreteDenoiser",
+                "params": {"num_idx": 1000, "weighting_config": wt, "scaling_config": sc, "discretization_config": dict(_DISC)}}
+    return {"target": f"{mod}denoiser.Denoiser", "params": {"weighting_config": wt, "scaling_config": sc}}
+
+
+def default_model_config(denoiser: dict = None) -> AttrDict:
+    """``denoiser``: a ``denoiser_config(...)`` dict in place of the default (DiscreteDenoiser, Eps/Eps)"""
     model = {
         "target": "sgm.models.diffusion.DiffusionEngine",
         "params": {
             "opt_keys": ["t_attn"], "input_key": "image", "scale_factor": 0.18215, "disable_first_stage_autocast": True,
-            "denoiser_config": {
-                "target": "sgm.modules.diffusionmodules.denoiser.DiscreteDenoiser",
-                "params": {"num_idx": 1000,
-                           "weighting_config": {"target": "sgm.modules.diffusionmodules.denoiser_weighting.EpsWeighting"},
-                           "scaling_config": {"target": "sgm.modules.diffusionmodules.denoiser_scaling.EpsScaling"},
-                           "discretization_config": dict(_DISC)}},
+            "denoiser_config": copy.deepcopy(denoiser) if denoiser is not None else denoiser_config(),
             "network_config": {
                 "target": "sgm.modules.diffusionmodules.openaimodel.UnifiedUNetModel",
                 "params": {"in_channels": 9, "out_channels": 4, "ctrl_channels": 0, "model_channels": 320,

@@ -1357,6 +1357,36 @@ __global__ void __launch_bounds__(256) diff_loss_grad_kernel(const float* __rest
   if (threadIdx.x == 0) loss[b] = tot / (4.0f * (float)hw);
 }
 
+// the same loss under any preconditioning and weighting (denoiser.py:28, denoiser_scaling.py, denoiser_weighting.py), per-sample host
+// coefficients: out = c_skip_b * noised + c_out_b * F; loss_b = mean(w_b (out - target)^2); seed of the reverse pass:
+// d (mean_b loss_b) / d F = 2 w_b c_out_b (out - target) / (B * C h w).  Layout and reduction as diff_loss_grad_kernel.
+__global__ void __launch_bounds__(256) precond_loss_grad_kernel(const float* __restrict__ f, const float* __restrict__ noised,
+                                                                const float* __restrict__ target, const float* __restrict__ c_skip,
+                                                                const float* __restrict__ c_out, const float* __restrict__ wgt,
+                                                                uint16_t* __restrict__ d_f, float* __restrict__ loss, int B, int hw,
+                                                                int ld_f, int cpad) {
+  __shared__ float red[4];
+  const int b = blockIdx.x;
+  const float cs = c_skip[b], co = c_out[b], w = wgt[b];
+  const float gscale = co * 2.0f * w / ((float)B * 4.0f * (float)hw);
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < hw; i += 256) {
+    float g4[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float out = fmaf(f[((long long)b * hw + i) * ld_f + c], co, cs * noised[((long long)b * 4 + c) * hw + i]);
+      const float r = out - target[((long long)b * 4 + c) * hw + i];
+      acc += w * r * r;
+      g4[c] = gscale * r;
+    }
+    uint16_t* dst = d_f + ((long long)b * hw + i) * cpad;
+    *reinterpret_cast<u32x2*>(dst) = u32x2{pack_bf16x2(g4[0], g4[1]), pack_bf16x2(g4[2], g4[3])};
+    for (int c = 4; c < cpad; c += 2) *reinterpret_cast<uint32_t*>(dst + c) = 0u;
+  }
+  const float tot = block_sum_256(acc, red);
+  if (threadIdx.x == 0) loss[b] = tot / (4.0f * (float)hw);
+}
+
 // torch.optim.AdamW (the reference's default optimizer, diffusion.py:49-51): decoupled weight decay, bias-corrected moments
 __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, long long n, float lr, float b1, float b2, float eps, float wd,
@@ -1740,6 +1770,18 @@ extern "C" int udt_diff_loss_grad(const float* eps, const float* noised, const f
   UDT_BWD_STREAM;
   hipLaunchKernelGGL(diff_loss_grad_kernel, dim3(B), dim3(256), 0, s, eps, noised, target, sigma, static_cast<uint16_t*>(d_eps), loss, B, hw,
                      ld_eps, cpad);
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}
+
+extern "C" int udt_precond_loss_grad(const float* f, const float* noised, const float* target, const float* c_skip, const float* c_out,
+                                     const float* w, void* d_f, float* loss, int32_t B, int32_t hw, int32_t ld_f, int32_t cpad,
+                                     void* stream) {
+  if (!f || !noised || !target || !c_skip || !c_out || !w || !d_f || !loss) return UDT_ERR_BAD_ARG;
+  if (B <= 0 || hw <= 0 || ld_f < 4 || cpad < 4 || cpad % 4 != 0) return UDT_ERR_BAD_SHAPE;
+  UDT_BWD_STREAM;
+  hipLaunchKernelGGL(precond_loss_grad_kernel, dim3(B), dim3(256), 0, s, f, noised, target, c_skip, c_out, w,
+                     static_cast<uint16_t*>(d_f), loss, B, hw, ld_f, cpad);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
 }

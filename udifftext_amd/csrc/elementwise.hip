@@ -6,6 +6,9 @@
 //   udt_cfg_sampler_step                : the same CFG denoise + the update of any sampler of sampling.py:140-215,423-567
 //                                         as one affine form (host coefficients: udifftext_amd/sgm/.../sampling.py)
 //   udt_cfg_multistep_step              : the same CFG denoise + LinearMultistepSampler's update, sampling.py:180-215
+//   udt_precond_unet_input / _euler_step / _sampler_step / _multistep_step
+//                                       : the same four launches under any denoiser_scaling.py:4-31 (c_skip, c_out, c_in from the host)
+//                                         and with or without the CFG pair (guiders.py:8-53: VanillaCFG / IdentityGuider)
 //   udt_posterior_sample                : distributions.py:24-41 (+ LatentEncoder scale, encoders/modules.py:1011-1014)
 //   udt_embed_tokens                    : encoders/modules.py:1069-1085,1160-1163
 //   udt_timestep_embedding              : diffusionmodules/util.py:206-230
@@ -17,7 +20,8 @@ namespace {
 
 // CHURN: x <- x + kn*noise first (the stochastic Euler step's pre-evaluation noise, sampling.py:328-331), written back in place;
 // the packed value is c_in times the STORED x, so a later plain udt_unet_input on x writes the same bits.
-template <bool CHURN>
+// PAIR: rows [0, B) and [B, 2B) of xin (the CFG pair) receive the value; else rows [0, B) only (unguided: IdentityGuider).
+template <bool CHURN, bool PAIR>
 __global__ void unet_input_kernel(float* __restrict__ x, const float* __restrict__ noise, uint16_t* __restrict__ xin, int B, int hw,
                                   int cpad, float c_in, float kn) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;   // (b, pixel)
@@ -40,50 +44,69 @@ __global__ void unet_input_kernel(float* __restrict__ x, const float* __restrict
   for (int c = 0; c < 4; ++c) v[c] *= c_in;
   const u32x2 pk = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
   *reinterpret_cast<u32x2*>(xin + ((long long)b * hw + pix) * cpad) = pk;
-  *reinterpret_cast<u32x2*>(xin + ((long long)(b + B) * hw + pix) * cpad) = pk;
+  if (PAIR) *reinterpret_cast<u32x2*>(xin + ((long long)(b + B) * hw + pix) * cpad) = pk;
 }
 
+// The preconditioned, guided denoised value of one element (denoiser.py:28, sampling_utils.py:8-9):
+//   den_{u,c} = c_skip*x + c_out*F_{u,c};  PAIR: den = den_u + scale*(den_c - den_u);  else den = c_skip*x + c_out*F (fu only).
+// The product and the two multiply-adds are written out, so that their contraction does not depend on the operands around them;
+// c_skip = 1 (EpsScaling) makes the product exact.
+template <bool PAIR>
+__device__ __forceinline__ float precond_den(float xv, float fu, float fc, float c_skip, float c_out, float scale) {
+  const float sx = c_skip * xv;
+  const float du = fmaf(fu, c_out, sx);                // network(...)*c_out + input*c_skip  (denoiser.py:28)
+  if (!PAIR) return du;
+  const float dc = fmaf(fc, c_out, sx);
+  return fmaf(scale, dc - du, du);                     // sampling_utils.py:8-9
+}
+
+// the network output rows of pixel (b, pix): PAIR: row b (unconditional) and row b + B (conditional) of [2B, hw, ld]; else row b of
+// [B, hw, ld] twice (the second is unused)
+template <bool PAIR>
+__device__ __forceinline__ void load_rows(const float* __restrict__ eps, int b, int B, int hw, int pix, int ld, f32x4& eu, f32x4& ec) {
+  eu = *reinterpret_cast<const f32x4*>(eps + ((long long)b * hw + pix) * ld);
+  ec = PAIR ? *reinterpret_cast<const f32x4*>(eps + ((long long)(b + B) * hw + pix) * ld) : eu;
+}
+
+template <bool PAIR>
 __global__ void cfg_euler_kernel(float* __restrict__ x, const float* __restrict__ eps, float* __restrict__ den_out,
-                                 int B, int hw, int ld, float c_out, float sigma, float sigma_next, float scale) {
+                                 int B, int hw, int ld, float c_skip, float c_out, float sigma, float sigma_next, float scale) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * hw) return;
   const int b = i / hw;
   const int pix = i - b * hw;
-  const f32x4 eu = *reinterpret_cast<const f32x4*>(eps + ((long long)b * hw + pix) * ld);
-  const f32x4 ec = *reinterpret_cast<const f32x4*>(eps + ((long long)(b + B) * hw + pix) * ld);
+  f32x4 eu, ec;
+  load_rows<PAIR>(eps, b, B, hw, pix, ld, eu, ec);
   float* xb = x + (long long)b * 4 * hw + pix;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const float xv = xb[c * hw];
-    const float du = eu[c] * c_out + xv;           // network(...)*c_out + input*c_skip  (denoiser.py:28)
-    const float dc = ec[c] * c_out + xv;
-    const float den = du + scale * (dc - du);         // sampling_utils.py:8-9
+    const float den = precond_den<PAIR>(xv, eu[c], ec[c], c_skip, c_out, scale);
     const float d = (xv - den) / sigma;               // to_d, sampling_utils.py:39-40
     xb[c * hw] = xv + d * (sigma_next - sigma);       // euler_step, sampling.py:85-86
     if (den_out) den_out[(long long)b * 4 * hw + c * hw + pix] = den;
   }
 }
 
-// Generic CFG sampler step: den as in cfg_euler_kernel, then
+// Generic sampler step: den as in cfg_euler_kernel, then
 //   xout = kx*xin + kd*den + ka*aux + kp*prev + kn*noise   (a null pointer drops its term),  den_out = den.
 // xout may alias xin or aux (each thread reads its pixel's inputs before it writes), so those carry no __restrict__.
+template <bool PAIR>
 __global__ void cfg_sampler_kernel(const float* xin, const float* __restrict__ eps, const float* aux,
                                    const float* __restrict__ prev, const float* __restrict__ noise, float* xout,
-                                   float* __restrict__ den_out, int B, int hw, int ld, udt_sampler_coefs k) {
+                                   float* __restrict__ den_out, int B, int hw, int ld, udt_sampler_coefs k, float c_skip) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * hw) return;
   const int b = i / hw;
   const int pix = i - b * hw;
-  const f32x4 eu = *reinterpret_cast<const f32x4*>(eps + ((long long)b * hw + pix) * ld);
-  const f32x4 ec = *reinterpret_cast<const f32x4*>(eps + ((long long)(b + B) * hw + pix) * ld);
+  f32x4 eu, ec;
+  load_rows<PAIR>(eps, b, B, hw, pix, ld, eu, ec);
   const long long base = (long long)b * 4 * hw + pix;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const long long o = base + (long long)c * hw;
     const float xv = xin[o];
-    const float du = eu[c] * k.c_out + xv;
-    const float dc = ec[c] * k.c_out + xv;
-    const float den = du + k.scale * (dc - du);
+    const float den = precond_den<PAIR>(xv, eu[c], ec[c], c_skip, k.c_out, k.scale);
     float acc = k.kx * xv + k.kd * den;
     if (aux) acc += k.ka * aux[o];
     if (prev) acc += k.kp * prev[o];
@@ -93,19 +116,20 @@ __global__ void cfg_sampler_kernel(const float* xin, const float* __restrict__ e
   }
 }
 
-// CFG linear-multistep step: den as in cfg_euler_kernel, d = (xin - den)/sigma, then
+// Linear-multistep step: den as in cfg_euler_kernel, d = (xin - den)/sigma, then
 //   xout = xin + (k[0]*d + k[1]*hist[1] + ... + k[n-1]*hist[n-1])   (summed in this order),  d_out = d.
 // xout may alias xin (each thread reads its pixel's inputs before it writes); d_out aliases none of the others.
 // Every load of the thread is issued before the first use: the history slots are guarded by the uniform bound n and
 // unrolled over the 8 slots, so hist[] is only indexed by constants and its loads overlap instead of queueing per slot.
+template <bool PAIR>
 __global__ void cfg_multistep_kernel(const float* xin, const float* __restrict__ eps, float* xout,
-                                     float* __restrict__ d_out, int B, int hw, int ld, udt_multistep_coefs k) {
+                                     float* __restrict__ d_out, int B, int hw, int ld, udt_multistep_coefs k, float c_skip) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * hw) return;
   const int b = i / hw;
   const int pix = i - b * hw;
-  const f32x4 eu = *reinterpret_cast<const f32x4*>(eps + ((long long)b * hw + pix) * ld);
-  const f32x4 ec = *reinterpret_cast<const f32x4*>(eps + ((long long)(b + B) * hw + pix) * ld);
+  f32x4 eu, ec;
+  load_rows<PAIR>(eps, b, B, hw, pix, ld, eu, ec);
   const long long base = (long long)b * 4 * hw + pix;
   float xv[4], hv[UDT_MULTISTEP_MAX][4] = {};
 #pragma unroll
@@ -119,9 +143,7 @@ __global__ void cfg_multistep_kernel(const float* xin, const float* __restrict__
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const long long o = base + (long long)c * hw;
-    const float du = eu[c] * k.c_out + xv[c];
-    const float dc = ec[c] * k.c_out + xv[c];
-    const float den = du + k.scale * (dc - du);
+    const float den = precond_den<PAIR>(xv[c], eu[c], ec[c], c_skip, k.c_out, k.scale);
     const float d = (xv[c] - den) / k.sigma;          // to_d, sampling_utils.py:39-40
     float acc = k.k[0] * d;
 #pragma unroll
@@ -321,43 +343,52 @@ inline unsigned nblk(long long n, int bs = 256) { return (unsigned)((n + bs - 1)
 
 #define UDT_STREAM hipStream_t s = reinterpret_cast<hipStream_t>(stream); UdtProfScope prof(5, s)
 
-extern "C" int udt_unet_input(const float* x, void* xin, int32_t B, int32_t hw, int32_t cpad, float c_in,
-                              void* stream) {
+// ---- the four sampler-step forms: one checked launcher each; the eps + CFG entry points call it with c_skip = 1, pair = 1 ----
+// ``strict``: the checks every entry point added since the first (16-byte aligned eps, B*hw <= 0x7fffffff, den_out aliasing)
+static int unet_input_impl(float* x, const float* noise, void* xin, int32_t B, int32_t hw, int32_t cpad, float c_in, float kn,
+                           bool pair, bool strict, void* stream) {
   if (!x || !xin) return UDT_ERR_BAD_ARG;
-  if (B <= 0 || hw <= 0 || cpad < 8 || cpad % 8 != 0) return UDT_ERR_BAD_SHAPE;
-  UDT_STREAM;
-  hipLaunchKernelGGL(unet_input_kernel<false>, dim3(nblk((long long)B * hw)), dim3(256), 0, s, const_cast<float*>(x),
-                     static_cast<const float*>(nullptr), reinterpret_cast<uint16_t*>(xin), B, hw, cpad, c_in, 0.f);
-  UDT_CHECK_LAUNCH();
-  return UDT_OK;
-}
-
-extern "C" int udt_unet_input_churn(float* x, const float* noise, void* xin, int32_t B, int32_t hw, int32_t cpad,
-                                    float c_in, float kn, void* stream) {
-  if (!x || !noise || !xin) return UDT_ERR_BAD_ARG;
   if (noise == x) return UDT_ERR_BAD_ARG;
-  if (B <= 0 || hw <= 0 || cpad < 8 || cpad % 8 != 0 || (long long)B * hw > 0x7fffffffLL) return UDT_ERR_BAD_SHAPE;
+  if (B <= 0 || hw <= 0 || cpad < 8 || cpad % 8 != 0) return UDT_ERR_BAD_SHAPE;
+  if (strict && (long long)B * hw > 0x7fffffffLL) return UDT_ERR_BAD_SHAPE;
   UDT_STREAM;
-  hipLaunchKernelGGL(unet_input_kernel<true>, dim3(nblk((long long)B * hw)), dim3(256), 0, s, x, noise,
-                     reinterpret_cast<uint16_t*>(xin), B, hw, cpad, c_in, kn);
+  const dim3 grid(nblk((long long)B * hw)), block(256);
+  uint16_t* o = reinterpret_cast<uint16_t*>(xin);
+  if (noise) {
+    if (pair) hipLaunchKernelGGL((unet_input_kernel<true, true>), grid, block, 0, s, x, noise, o, B, hw, cpad, c_in, kn);
+    else hipLaunchKernelGGL((unet_input_kernel<true, false>), grid, block, 0, s, x, noise, o, B, hw, cpad, c_in, kn);
+  } else {
+    if (pair) hipLaunchKernelGGL((unet_input_kernel<false, true>), grid, block, 0, s, x, noise, o, B, hw, cpad, c_in, 0.f);
+    else hipLaunchKernelGGL((unet_input_kernel<false, false>), grid, block, 0, s, x, noise, o, B, hw, cpad, c_in, 0.f);
+  }
   UDT_CHECK_LAUNCH();
   return UDT_OK;
 }
 
-extern "C" int udt_cfg_euler_step(float* x, const float* eps, float* denoised_out, int32_t B, int32_t hw,
-                                  int32_t ld_eps, float c_out, float sigma, float sigma_next, float cfg_scale, void* stream) {
+static int euler_step_impl(float* x, const float* eps, float* denoised_out, int32_t B, int32_t hw, int32_t ld_eps, float c_skip,
+                           float c_out, float sigma, float sigma_next, float cfg_scale, bool pair, bool strict, void* stream) {
   if (!x || !eps) return UDT_ERR_BAD_ARG;
   if (B <= 0 || hw <= 0 || ld_eps < 4 || ld_eps % 4 != 0 || sigma == 0.f) return UDT_ERR_BAD_SHAPE;
+  if (strict) {
+    if ((long long)B * hw > 0x7fffffffLL || reinterpret_cast<uintptr_t>(eps) % 16 != 0) return UDT_ERR_BAD_SHAPE;
+    // den_out is written while x is read by other threads: it may not alias it
+    if (denoised_out == x) return UDT_ERR_BAD_ARG;
+  }
   UDT_STREAM;
-  hipLaunchKernelGGL(cfg_euler_kernel, dim3(nblk((long long)B * hw)), dim3(256), 0, s, x, eps, denoised_out, B, hw,
-                     ld_eps, c_out, sigma, sigma_next, cfg_scale);
+  const dim3 grid(nblk((long long)B * hw)), block(256);
+  if (pair)
+    hipLaunchKernelGGL(cfg_euler_kernel<true>, grid, block, 0, s, x, eps, denoised_out, B, hw, ld_eps, c_skip, c_out, sigma,
+                       sigma_next, cfg_scale);
+  else
+    hipLaunchKernelGGL(cfg_euler_kernel<false>, grid, block, 0, s, x, eps, denoised_out, B, hw, ld_eps, c_skip, c_out, sigma,
+                       sigma_next, cfg_scale);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
 }
 
-extern "C" int udt_cfg_sampler_step(const float* xin, const float* eps, const float* aux, const float* prev,
-                                    const float* noise, float* xout, float* denoised_out, int32_t B, int32_t hw,
-                                    int32_t ld_eps, udt_sampler_coefs k, void* stream) {
+static int sampler_step_impl(const float* xin, const float* eps, const float* aux, const float* prev, const float* noise,
+                             float* xout, float* denoised_out, int32_t B, int32_t hw, int32_t ld_eps, udt_sampler_coefs k,
+                             float c_skip, bool pair, void* stream) {
   if (!xin || !eps || !xout) return UDT_ERR_BAD_ARG;
   if (B <= 0 || hw <= 0 || ld_eps < 4 || ld_eps % 4 != 0 || (long long)B * hw > 0x7fffffffLL) return UDT_ERR_BAD_SHAPE;
   if (reinterpret_cast<uintptr_t>(eps) % 16 != 0) return UDT_ERR_BAD_SHAPE;
@@ -365,14 +396,19 @@ extern "C" int udt_cfg_sampler_step(const float* xin, const float* eps, const fl
   if (denoised_out && (denoised_out == xin || denoised_out == aux || denoised_out == prev || denoised_out == xout))
     return UDT_ERR_BAD_ARG;
   UDT_STREAM;
-  hipLaunchKernelGGL(cfg_sampler_kernel, dim3(nblk((long long)B * hw)), dim3(256), 0, s, xin, eps, aux, prev, noise, xout,
-                     denoised_out, B, hw, ld_eps, k);
+  const dim3 grid(nblk((long long)B * hw)), block(256);
+  if (pair)
+    hipLaunchKernelGGL(cfg_sampler_kernel<true>, grid, block, 0, s, xin, eps, aux, prev, noise, xout, denoised_out, B, hw, ld_eps,
+                       k, c_skip);
+  else
+    hipLaunchKernelGGL(cfg_sampler_kernel<false>, grid, block, 0, s, xin, eps, aux, prev, noise, xout, denoised_out, B, hw, ld_eps,
+                       k, c_skip);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
 }
 
-extern "C" int udt_cfg_multistep_step(const float* xin, const float* eps, float* xout, float* d_out, int32_t B,
-                                      int32_t hw, int32_t ld_eps, udt_multistep_coefs k, void* stream) {
+static int multistep_step_impl(const float* xin, const float* eps, float* xout, float* d_out, int32_t B, int32_t hw,
+                               int32_t ld_eps, udt_multistep_coefs k, float c_skip, bool pair, void* stream) {
   if (!xin || !eps || !xout || !d_out) return UDT_ERR_BAD_ARG;
   if (k.n < 1 || k.n > UDT_MULTISTEP_MAX) return UDT_ERR_BAD_ARG;
   if (B <= 0 || hw <= 0 || ld_eps < 4 || ld_eps % 4 != 0 || (long long)B * hw > 0x7fffffffLL || k.sigma == 0.f)
@@ -383,10 +419,60 @@ extern "C" int udt_cfg_multistep_step(const float* xin, const float* eps, float*
   for (int j = 1; j < k.n; ++j)
     if (!k.hist[j] || k.hist[j] == d_out) return UDT_ERR_BAD_ARG;
   UDT_STREAM;
-  hipLaunchKernelGGL(cfg_multistep_kernel, dim3(nblk((long long)B * hw)), dim3(256), 0, s, xin, eps, xout, d_out, B, hw,
-                     ld_eps, k);
+  const dim3 grid(nblk((long long)B * hw)), block(256);
+  if (pair) hipLaunchKernelGGL(cfg_multistep_kernel<true>, grid, block, 0, s, xin, eps, xout, d_out, B, hw, ld_eps, k, c_skip);
+  else hipLaunchKernelGGL(cfg_multistep_kernel<false>, grid, block, 0, s, xin, eps, xout, d_out, B, hw, ld_eps, k, c_skip);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
+}
+
+extern "C" int udt_unet_input(const float* x, void* xin, int32_t B, int32_t hw, int32_t cpad, float c_in,
+                              void* stream) {
+  return unet_input_impl(const_cast<float*>(x), nullptr, xin, B, hw, cpad, c_in, 0.f, true, false, stream);
+}
+
+extern "C" int udt_unet_input_churn(float* x, const float* noise, void* xin, int32_t B, int32_t hw, int32_t cpad,
+                                    float c_in, float kn, void* stream) {
+  if (!noise) return UDT_ERR_BAD_ARG;
+  return unet_input_impl(x, noise, xin, B, hw, cpad, c_in, kn, true, true, stream);
+}
+
+extern "C" int udt_precond_unet_input(float* x, const float* noise, void* xin, int32_t B, int32_t hw, int32_t cpad, float c_in,
+                                      float kn, int32_t pair, void* stream) {
+  return unet_input_impl(x, noise, xin, B, hw, cpad, c_in, kn, pair != 0, true, stream);
+}
+
+extern "C" int udt_cfg_euler_step(float* x, const float* eps, float* denoised_out, int32_t B, int32_t hw,
+                                  int32_t ld_eps, float c_out, float sigma, float sigma_next, float cfg_scale, void* stream) {
+  return euler_step_impl(x, eps, denoised_out, B, hw, ld_eps, 1.0f, c_out, sigma, sigma_next, cfg_scale, true, false, stream);
+}
+
+extern "C" int udt_precond_euler_step(float* x, const float* f, float* denoised_out, int32_t B, int32_t hw, int32_t ld_f,
+                                      float c_skip, float c_out, float sigma, float sigma_next, float cfg_scale, int32_t pair,
+                                      void* stream) {
+  return euler_step_impl(x, f, denoised_out, B, hw, ld_f, c_skip, c_out, sigma, sigma_next, cfg_scale, pair != 0, true, stream);
+}
+
+extern "C" int udt_cfg_sampler_step(const float* xin, const float* eps, const float* aux, const float* prev,
+                                    const float* noise, float* xout, float* denoised_out, int32_t B, int32_t hw,
+                                    int32_t ld_eps, udt_sampler_coefs k, void* stream) {
+  return sampler_step_impl(xin, eps, aux, prev, noise, xout, denoised_out, B, hw, ld_eps, k, 1.0f, true, stream);
+}
+
+extern "C" int udt_precond_sampler_step(const float* xin, const float* f, const float* aux, const float* prev,
+                                        const float* noise, float* xout, float* denoised_out, int32_t B, int32_t hw,
+                                        int32_t ld_f, udt_sampler_coefs k, float c_skip, int32_t pair, void* stream) {
+  return sampler_step_impl(xin, f, aux, prev, noise, xout, denoised_out, B, hw, ld_f, k, c_skip, pair != 0, stream);
+}
+
+extern "C" int udt_cfg_multistep_step(const float* xin, const float* eps, float* xout, float* d_out, int32_t B,
+                                      int32_t hw, int32_t ld_eps, udt_multistep_coefs k, void* stream) {
+  return multistep_step_impl(xin, eps, xout, d_out, B, hw, ld_eps, k, 1.0f, true, stream);
+}
+
+extern "C" int udt_precond_multistep_step(const float* xin, const float* f, float* xout, float* d_out, int32_t B, int32_t hw,
+                                          int32_t ld_f, udt_multistep_coefs k, float c_skip, int32_t pair, void* stream) {
+  return multistep_step_impl(xin, f, xout, d_out, B, hw, ld_f, k, c_skip, pair != 0, stream);
 }
 
 extern "C" int udt_posterior_sample(const float* moments, const float* noise, float* z, int32_t B, int32_t hw,

@@ -117,6 +117,10 @@ SYMBOLS = {
     "udt_cfg_euler_step": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
     "udt_cfg_sampler_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, SamplerCoefs, _vp]),
     "udt_cfg_multistep_step": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, MultistepCoefs, _vp]),
+    "udt_precond_unet_input": (C.c_int, [_fp, _fp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp]),
+    "udt_precond_euler_step": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
+    "udt_precond_sampler_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, SamplerCoefs, _f32, _i32, _vp]),
+    "udt_precond_multistep_step": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, MultistepCoefs, _f32, _i32, _vp]),
     "udt_sampler_step": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
     "udt_posterior_sample": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _f32, _vp]),
     "udt_nchw_to_nhwc": (C.c_int, [_fp, _vp, _i32, _i32, _i64, _i32, _f32, _vp]),
@@ -153,6 +157,7 @@ SYMBOLS = {
     "udt_local_loss_seg_bwd_hw": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32,
                                             _vp]),
     "udt_diff_loss_grad": (C.c_int, [_fp, _fp, _fp, _fp, _vp, _fp, _i32, _i32, _i32, _i32, _vp]),
+    "udt_precond_loss_grad": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _i32, _i32, _i32, _i32, _vp]),
     "udt_adamw_f32": (C.c_int, [_fp, _fp, _fp, _fp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp]),
     "udt_add_bf16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "udt_debug_set": (C.c_int, [C.c_char_p, _i32]),

@@ -823,6 +823,76 @@ def cfg_multistep_step(xin: torch.Tensor, eps: torch.Tensor, c_out: float, scale
     return out
 
 
+# ---- the same launches under any preconditioning, with or without the CFG pair (udt_precond_*)
+def _check_step_args(xin: torch.Tensor, f: torch.Tensor, pair: bool, what: str, *others) -> tuple:
+    """shapes of one udt_precond_* step: xin and ``others`` fp32 NCHW [B,4,h,w] contiguous, f fp32 NHWC [(2B if pair else B), h, w, ld]"""
+    B, _, h, w = xin.shape
+    for t in (xin, *others):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, 4, h, w)):
+            raise ValueError(f"{what}: fp32 NCHW [B,4,h,w] contiguous tensors")
+    rows = 2 * B if pair else B
+    if f.dtype != torch.float32 or not f.is_contiguous() or f.dim() != 4 or tuple(f.shape[:-1]) != (rows, h, w):
+        raise ValueError(f"{what}: the network output must be fp32 [{rows}, {h}, {w}, ld] ({'CFG pair' if pair else 'unguided'}), "
+                         f"got {tuple(f.shape)}")
+    return B, h * w, f.shape[-1]
+
+
+def precond_unet_input(x: torch.Tensor, xin: torch.Tensor, c_in: float, pair: bool = True, noise: Optional[torch.Tensor] = None,
+                       kn: float = 0.0) -> None:
+    """one launch of udt_precond_unet_input: channels 0..3 of xin's rows [0, B) (and [B, 2B) if ``pair``) = x * c_in; ``noise``:
+    the churned form, x <- x + kn*noise in place first"""
+    B, _, h, w = x.shape
+    rows = 2 * B if pair else B
+    for t in (x, noise):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, 4, h, w)):
+            raise ValueError("precond_unet_input: fp32 NCHW [B,4,h,w] contiguous tensors")
+    if xin.dtype != torch.bfloat16 or not xin.is_contiguous() or tuple(xin.shape[:-1]) != (rows, h, w):
+        raise ValueError(f"precond_unet_input: xin must be bf16 [{rows}, {h}, {w}, cpad] ({'CFG pair' if pair else 'unguided'}), "
+                         f"got {tuple(xin.shape)}")
+    L.check(L.load().udt_precond_unet_input(_ptr(x), _ptr(noise), _ptr(xin), B, h * w, xin.shape[-1], c_in, kn, int(pair),
+                                            _stream()), "udt_precond_unet_input")
+
+
+def precond_euler_step(x: torch.Tensor, f: torch.Tensor, c_skip: float, c_out: float, sigma: float, sigma_next: float,
+                       scale: float = 0.0, pair: bool = True, denoised: Optional[torch.Tensor] = None) -> None:
+    """one launch of udt_precond_euler_step: den = guided(c_skip*x + c_out*F); x += (x - den)/sigma * (sigma_next - sigma)"""
+    B, hw, ld = _check_step_args(x, f, pair, "precond_euler_step", denoised)
+    L.check(L.load().udt_precond_euler_step(_ptr(x), _ptr(f), _ptr(denoised), B, hw, ld, c_skip, c_out, sigma, sigma_next, scale,
+                                            int(pair), _stream()), "udt_precond_euler_step")
+
+
+def precond_sampler_step(xin: torch.Tensor, f: torch.Tensor, c_skip: float, c_out: float, scale: float = 0.0, pair: bool = True,
+                         kx: float = 0.0, kd: float = 0.0, aux: Optional[torch.Tensor] = None, ka: float = 0.0,
+                         prev: Optional[torch.Tensor] = None, kp: float = 0.0, noise: Optional[torch.Tensor] = None, kn: float = 0.0,
+                         out: Optional[torch.Tensor] = None, denoised: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """one launch of udt_precond_sampler_step: cfg_sampler_step's update on den = guided(c_skip*xin + c_out*F)"""
+    out = xin if out is None else out
+    B, hw, ld = _check_step_args(xin, f, pair, "precond_sampler_step", aux, prev, noise, out, denoised)
+    k = L.SamplerCoefs(kx, kd, ka, kp, kn, c_out, scale)
+    L.check(L.load().udt_precond_sampler_step(_ptr(xin), _ptr(f), _ptr(aux), _ptr(prev), _ptr(noise), _ptr(out), _ptr(denoised),
+                                              B, hw, ld, k, c_skip, int(pair), _stream()), "udt_precond_sampler_step")
+    return out
+
+
+def precond_multistep_step(xin: torch.Tensor, f: torch.Tensor, c_skip: float, c_out: float, scale: float, pair: bool, sigma: float,
+                           coefs: Sequence[float], hist: Sequence[torch.Tensor] = (), d_out: Optional[torch.Tensor] = None,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """one launch of udt_precond_multistep_step: cfg_multistep_step's update on den = guided(c_skip*xin + c_out*F)"""
+    out = xin if out is None else out
+    n = len(coefs)
+    if not (1 <= n <= L.MULTISTEP_MAX and len(hist) == n - 1) or d_out is None:
+        raise ValueError("precond_multistep_step: n = len(coefs) in 1..8, len(hist) = n - 1 and d_out is required")
+    B, hw, ld = _check_step_args(xin, f, pair, "precond_multistep_step", out, d_out, *hist)
+    k = L.MultistepCoefs(c_out, scale, sigma, n)
+    for j, c in enumerate(coefs):
+        k.k[j] = c
+    for j, t in enumerate(hist):
+        k.hist[j + 1] = _ptr(t)
+    L.check(L.load().udt_precond_multistep_step(_ptr(xin), _ptr(f), _ptr(out), _ptr(d_out), B, hw, ld, k, c_skip, int(pair),
+                                                _stream()), "udt_precond_multistep_step")
+    return out
+
+
 def posterior_sample(moments: torch.Tensor, noise: torch.Tensor, scale: float) -> torch.Tensor:
     """moments fp32 NHWC [B, h, w, ld>=8]; noise fp32 NCHW [B,4,h,w] -> z fp32 NCHW."""
     B, h, w, ld = moments.shape
@@ -1183,6 +1253,22 @@ def diff_loss_grad(eps: torch.Tensor, noised: torch.Tensor, target: torch.Tensor
     L.check(L.load().udt_diff_loss_grad(_ptr(eps), _ptr(noised), _ptr(target), _ptr(sigma), _ptr(d_eps), _ptr(loss), B, h * w, ld, cpad,
                                         _stream()), "udt_diff_loss_grad")
     return loss, d_eps
+
+
+def precond_loss_grad(f: torch.Tensor, noised: torch.Tensor, target: torch.Tensor, c_skip: torch.Tensor, c_out: torch.Tensor,
+                      w: torch.Tensor, cpad: int = 64):
+    """(loss fp32 [B], d_f bf16 NHWC [B, h, w, cpad]) of mean(w_b (c_skip_b*noised + c_out_b*F - target)^2): udt_precond_loss_grad;
+    f fp32 NHWC [B, h, w, ld], noised / target fp32 NCHW, c_skip / c_out / w fp32 [B] on the device"""
+    B, h, ww, ld = f.shape
+    assert f.dtype == torch.float32 and f.is_contiguous() and noised.is_contiguous() and target.is_contiguous()
+    assert noised.shape == (B, 4, h, ww) == target.shape
+    for t in (c_skip, c_out, w):
+        assert t.dtype == torch.float32 and t.numel() == B and t.is_contiguous() and t.device == f.device
+    d_f = torch.empty((B, h, ww, cpad), dtype=torch.bfloat16, device=f.device)
+    loss = torch.empty((B,), dtype=torch.float32, device=f.device)
+    L.check(L.load().udt_precond_loss_grad(_ptr(f), _ptr(noised), _ptr(target), _ptr(c_skip), _ptr(c_out), _ptr(w), _ptr(d_f),
+                                           _ptr(loss), B, h * ww, ld, cpad, _stream()), "udt_precond_loss_grad")
+    return loss, d_f
 
 
 def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,

@@ -17,12 +17,13 @@ from udifftext_amd import config as C
 from udifftext_amd import rng, synth
 
 
-def build_engine(device: torch.device, synthetic_weights: bool = True, verbose: bool = False):
+def build_engine(device: torch.device, synthetic_weights: bool = True, verbose: bool = False, denoiser: Optional[dict] = None):
     """instantiate the DiffusionEngine from the (code-built) model config, fill deterministic synthetic weights
-    (there are no checkpoints here), move it to the GPU, eval + freeze — reference util.py:7-22."""
+    (there are no checkpoints here), move it to the GPU, eval + freeze — reference util.py:7-22.  ``denoiser``: a
+    ``config.denoiser_config(...)`` dict (v-prediction, EDM, the continuous Denoiser) in place of the default eps one."""
     from sgm.util import instantiate_from_config, skip_param_init
     t0 = time.time()
-    cfg = C.default_model_config()
+    cfg = C.default_model_config(denoiser)
     if synthetic_weights:
         with skip_param_init():
             model = instantiate_from_config(cfg.model)
@@ -46,22 +47,34 @@ SAMPLERS = {
     "dpmpp2s_a": "DPMPP2SAncestralSampler",
     "linear_multistep": "LinearMultistepSampler",
 }
+GUIDERS = {"vanilla_cfg": "VanillaCFG", "identity": "IdentityGuider"}
+DISCRETIZATIONS = {"legacy_ddpm": "LegacyDDPMDiscretization", "edm": "EDMDiscretization"}
 
 
 def init_sampling(steps: int, scale: float, device: torch.device, verbose: bool = False, sampler: str = "euler", *,
-                  s_churn: float = 0.0, s_tmin: float = 0.0, s_tmax: float = 999.0, s_noise: float = 1.0):
+                  s_churn: float = 0.0, s_tmin: float = 0.0, s_tmax: float = 999.0, s_noise: float = 1.0,
+                  guider: str = "vanilla_cfg", discretization: str = "legacy_ddpm", discretization_params: Optional[dict] = None):
     """reference util.py:24-47: EulerEDMSampler + LegacyDDPMDiscretization + VanillaCFG(scale).  ``sampler`` picks another
     sampler of the reference's sampling.py with the same discretization and guider (SAMPLERS; their default parameters:
     eta = s_noise = 1 for the ancestral ones, order = 4 for linear_multistep).  ``s_churn`` / ``s_tmin`` / ``s_tmax`` / ``s_noise``
-    (the Karras churn settings, reference sampling.py:89-98) go to "euler" and "heun"; Euler runs s_churn > 0, Heun refuses it"""
+    (the Karras churn settings, reference sampling.py:89-98) go to "euler" and "heun"; Euler runs s_churn > 0, Heun refuses it.
+    ``guider``: "vanilla_cfg" (VanillaCFG(scale)) or "identity" (IdentityGuider: unguided, the UNet runs on the conditional rows
+    only and ``scale`` is not used); ``discretization``: "legacy_ddpm" or "edm" (EDMDiscretization), with ``discretization_params``
+    as its constructor arguments"""
     from sgm.modules.diffusionmodules import sampling as S
     if sampler not in SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}; one of {sorted(SAMPLERS)}")
-    common = dict(
-        num_steps=steps,
-        discretization_config={"target": "sgm.modules.diffusionmodules.discretizer.LegacyDDPMDiscretization"},
-        guider_config={"target": "sgm.modules.diffusionmodules.guiders.VanillaCFG", "params": {"scale": scale}},
-        verbose=verbose, device=device)
+    if guider not in GUIDERS:
+        raise ValueError(f"unknown guider {guider!r}; one of {sorted(GUIDERS)}")
+    if discretization not in DISCRETIZATIONS:
+        raise ValueError(f"unknown discretization {discretization!r}; one of {sorted(DISCRETIZATIONS)}")
+    disc = {"target": "sgm.modules.diffusionmodules.discretizer." + DISCRETIZATIONS[discretization]}
+    if discretization_params:
+        disc["params"] = dict(discretization_params)
+    guide = {"target": "sgm.modules.diffusionmodules.guiders." + GUIDERS[guider]}
+    if guider == "vanilla_cfg":
+        guide["params"] = {"scale": scale}
+    common = dict(num_steps=steps, discretization_config=disc, guider_config=guide, verbose=verbose, device=device)
     if sampler in ("euler", "heun"):
         common.update(s_churn=s_churn, s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise)
     return getattr(S, SAMPLERS[sampler])(**common)

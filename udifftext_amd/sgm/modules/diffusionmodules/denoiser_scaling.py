@@ -1,5 +1,14 @@
-"""Preconditioning coefficients (reference sgm/modules/diffusionmodules/denoiser_scaling.py:16-22)."""
+"""Preconditioning coefficients (reference sgm/modules/diffusionmodules/denoiser_scaling.py:4-31)."""
 import torch
+
+
+class EDMScaling:
+    def __init__(self, sigma_data=0.5):
+        self.sigma_data = sigma_data
+
+    def __call__(self, sigma: torch.Tensor):
+        denom = sigma ** 2 + self.sigma_data ** 2
+        return self.sigma_data ** 2 / denom, sigma * self.sigma_data / denom ** 0.5, 1 / denom ** 0.5, 0.25 * sigma.log()
 
 
 class EpsScaling:

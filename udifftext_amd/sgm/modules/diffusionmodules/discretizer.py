@@ -1,6 +1,6 @@
 """Sigma discretisation (host-side, fp64 table -> fp32 sigmas).
 
-Follows reference sgm/modules/diffusionmodules/discretizer.py:10-13,16-20,41-68 and
+Follows reference sgm/modules/diffusionmodules/discretizer.py:10-13,16-20,27-38,41-68 and
 make_beta_schedule (sgm/modules/diffusionmodules/util.py:19-32): linear-beta DDPM schedule,
 ``sigma = sqrt((1 - abar) / abar)`` cast to fp32 before the square root, n-step sub-sampling by
 ``linspace(999, 0, n, endpoint=False).astype(int)[::-1]``.
@@ -27,6 +27,18 @@ class Discretization:
 
     def get_sigmas(self, n, device):
         raise NotImplementedError
+
+
+class EDMDiscretization(Discretization):
+    """Karras et al.: sigma_i = (max^(1/rho) + i/(n-1) (min^(1/rho) - max^(1/rho)))^rho, descending"""
+
+    def __init__(self, sigma_min=0.02, sigma_max=80.0, rho=7.0):
+        self.sigma_min, self.sigma_max, self.rho = sigma_min, sigma_max, rho
+
+    def get_sigmas(self, n, device="cpu"):
+        ramp = torch.linspace(0, 1, n, device=device)
+        min_inv_rho, max_inv_rho = self.sigma_min ** (1 / self.rho), self.sigma_max ** (1 / self.rho)
+        return (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** self.rho
 
 
 class LegacyDDPMDiscretization(Discretization):

@@ -19,6 +19,11 @@ DPMPP2SAncestralSampler, DPMPP2MSampler, reference :140-215, :423-567) or ``Mult
 LinearMultistepSampler, reference :180-215; to_d and the sum over a ring of derivative buffers).  One loop (``_PlanSampler``)
 runs the plans of any of them as eager launches or hipGraph replays (``_GraphedSteps``): alone, on a lane of
 pipeline.predict_many, or as several batches in flight.
+
+Preconditioning and guidance: the host scalars of an evaluation come from ``precond_coefs`` (EpsScaling, VScaling,
+EDMScaling under Denoiser or DiscreteDenoiser).  EpsScaling + DiscreteDenoiser + VanillaCFG runs the udt_cfg_* launches above;
+every other combination, IdentityGuider (B rows through the UNet, no pair) included, runs the udt_precond_* forms of the same
+kernels, launch for launch.  Unknown denoiser / scaling / guider classes and dynamic thresholding raise.
 """
 from __future__ import annotations
 
@@ -32,8 +37,10 @@ import torch
 from udifftext_amd import ops, packing, rng
 
 from ...util import default, instantiate_from_config, require_gpu
-from .guiders import VanillaCFG
-from .sampling_utils import to_d
+from .denoiser import Denoiser, DiscreteDenoiser
+from .denoiser_scaling import EDMScaling, EpsScaling, VScaling
+from .guiders import IdentityGuider, VanillaCFG
+from .sampling_utils import NoDynamicThresholding, to_d
 
 DEFAULT_GUIDER = {"target": "sgm.modules.diffusionmodules.guiders.IdentityGuider"}
 
@@ -98,6 +105,78 @@ def _all_zero(t: torch.Tensor) -> bool:
     (``_udt_all_zero``); anything else is asked on the device (one host sync)"""
     flag = getattr(t, "_udt_all_zero", None)
     return bool(flag) if flag is not None else not bool(t.any())
+
+
+class Precond(NamedTuple):
+    """denoiser.py:23-28 for one host sigma: D(x) = c_skip*x + c_out*F(c_in*x, c_noise)"""
+    c_skip: float
+    c_out: float
+    c_in: float
+    c_noise: float                     # the network's timestep input: a table index (as a float) or a real number
+
+
+def _quantise(table: torch.Tensor, value: float):
+    idx = int((table - value).abs().argmin())
+    return idx, float(table[idx])
+
+
+def check_denoiser(denoiser) -> None:
+    """raise for a denoiser or scaling class ``precond_coefs`` has no formula for (host only: no device data is read)"""
+    if type(denoiser) not in (Denoiser, DiscreteDenoiser):
+        raise NotImplementedError(f"the fused MI355X step implements Denoiser and DiscreteDenoiser, not {type(denoiser).__name__}")
+    if type(denoiser.scaling) not in (EpsScaling, VScaling, EDMScaling):
+        raise NotImplementedError(f"the fused MI355X step implements EpsScaling, VScaling and EDMScaling, not "
+                                  f"{type(denoiser.scaling).__name__}")
+
+
+def precond_coefs(denoiser, sigma: float, table: Optional[torch.Tensor] = None) -> Precond:
+    """the host form of ``denoiser.__call__``'s scalars (reference denoiser.py:23-28), in float64 from the fp32 table entries:
+    DiscreteDenoiser quantises sigma on its table (``table``: its host copy), applies the scaling, then quantises c_noise
+    (EDMScaling: the nearest table entry to 0.25 ln sigma_q, as the reference does); the plain Denoiser quantises nothing and
+    c_noise is a real number.  Dispatches on the EXACT denoiser and scaling class: a subclass may compute anything."""
+    check_denoiser(denoiser)
+    if type(denoiser) is DiscreteDenoiser:
+        table = denoiser.sigmas.detach().float().cpu() if table is None else table
+        s = _quantise(table, sigma)[1]
+    else:
+        s = float(sigma)
+    scaling = denoiser.scaling
+    if type(scaling) is EpsScaling:
+        p = Precond(1.0, -s, 1.0 / (s * s + 1.0) ** 0.5, s)
+    elif type(scaling) is VScaling:
+        d = s * s + 1.0
+        p = Precond(1.0 / d, -s / d ** 0.5, 1.0 / d ** 0.5, s)
+    else:
+        sd = float(scaling.sigma_data)
+        d = s * s + sd * sd
+        log_s = float(torch.log(torch.tensor(s, dtype=torch.float64)))     # (torch's log, as the reference takes it)
+        p = Precond(sd * sd / d, s * sd / d ** 0.5, 1.0 / d ** 0.5, 0.25 * log_s)
+    if type(denoiser) is DiscreteDenoiser and denoiser.quantize_c_noise:
+        p = p._replace(c_noise=float(_quantise(table, p.c_noise)[0]))
+    return p
+
+
+def _table_key(denoiser):
+    """the CONTENT of a DiscreteDenoiser's sigma table (None for the plain Denoiser): its bytes, read from the device once per
+    (buffer, version) and kept on the denoiser object — no host synchronisation on later calls, and no address that a freed
+    denoiser's successor could share"""
+    sigmas = getattr(denoiser, "sigmas", None)
+    if sigmas is None:
+        return None
+    state = (sigmas.data_ptr(), sigmas._version)
+    cached = denoiser.__dict__.get("_udt_table_key")
+    if cached is None or cached[0] != state:
+        cached = (state, hash(sigmas.detach().float().cpu().numpy().tobytes()))
+        denoiser.__dict__["_udt_table_key"] = cached
+    return cached[1]
+
+
+def denoiser_key(denoiser) -> tuple:
+    """what the host coefficients of a run depend on — the denoiser and scaling classes, the scaling's parameters, the quantise flag
+    and the sigma table's content: captured graphs bake the coefficients in, so the runner caches are keyed by it"""
+    sc = denoiser.scaling
+    return (type(denoiser).__name__, type(sc).__name__, tuple(sorted((k, float(v)) for k, v in vars(sc).items())),
+            bool(getattr(denoiser, "quantize_c_noise", False)), _table_key(denoiser))
 
 
 def weights_fingerprint(model) -> int:
@@ -201,25 +280,33 @@ def plans_add_noise(plans) -> bool:
 class _Stepper:
     """Step-invariant device state of one sampling run + the fused per-step launch sequence."""
 
-    def __init__(self, model, cond: dict, uc: dict, batch_size: int, latent_hw, scale: float, two_streams=None):
+    def __init__(self, model, cond: dict, uc: dict, batch_size: int, latent_hw, scale: float, two_streams=None, pair: bool = True):
+        """pair: the CFG pair (VanillaCFG: 2B rows, uncond first); False: IdentityGuider — B rows built from ``cond`` only, no
+        zero-context shortcut and no two-stream split"""
         self.engine = model
         self.unet = model.model.diffusion_model
         self.scale = float(scale)
         self.B = batch_size
+        self.pair = bool(pair)
+        self.rows = 2 * batch_size if self.pair else batch_size
         h, w = latent_hw
         dev = cond["concat"].device
-        self.table = model.denoiser.sigmas.detach().float().cpu()          # ascending 1000-entry table
-        ctx = torch.cat((uc["t_crossattn"], cond["t_crossattn"]), 0)
+        self.den = model.denoiser
+        sigmas = getattr(self.den, "sigmas", None)
+        self.table = sigmas.detach().float().cpu() if sigmas is not None else None     # ascending 1000-entry table
+        # EpsScaling + DiscreteDenoiser + VanillaCFG: the udt_cfg_* launches; anything else: udt_precond_* (same count per evaluation)
+        self.eps_cfg = self.pair and type(self.den) is DiscreteDenoiser and type(self.den.scaling) is EpsScaling
+        ctx = torch.cat((uc["t_crossattn"], cond["t_crossattn"]), 0) if self.pair else cond["t_crossattn"]
         self.t_kv = self.unet.project_context(ctx)                        # hoisted k|v of all transformers
         self.t_fused = self.unet.prepare_fused_tattn(self.t_kv)           # ... folded further into the fused t_attn tables
         # force_uc_zero_embeddings=["label"] (reference sample loop) makes the unconditional context exactly zero:
         # its cross-attention is then x + to_out.bias — one host sync per sampling run buys half of every t_attn
-        self.zero_ctx_rows = batch_size if _all_zero(uc["t_crossattn"]) else 0
+        self.zero_ctx_rows = batch_size if self.pair and _all_zero(uc["t_crossattn"]) else 0
         # two launch streams: the unconditional and the conditional half of the CFG pair never meet before the
         # guidance step, so each runs the UNet on its own HIP stream, planned for half of the CUs.  Measured on
         # MI355X: one stream leaves the chip idle during every kernel's ramp-up / epilogue / tail (a half-GPU plan
         # alone is only 24 % slower than the whole-GPU plan); two concurrent streams fill those holes.
-        self.dual = DUAL_STREAM if two_streams is None else bool(two_streams)
+        self.dual = self.pair and (DUAL_STREAM if two_streams is None else bool(two_streams))
         if self.dual:
             self.side = torch.cuda.Stream(device=dev)
             self.eps = torch.empty((2 * batch_size, h, w, 4), dtype=torch.float32, device=dev)
@@ -227,10 +314,10 @@ class _Stepper:
             self.t_kv_c = [[kv[batch_size:] for kv in lst] for lst in self.t_kv]
             self.t_fused_u = [[tb.rows(0, batch_size) if tb is not None else None for tb in lst] for lst in self.t_fused]
             self.t_fused_c = [[tb.rows(batch_size) if tb is not None else None for tb in lst] for lst in self.t_fused]
-        self.xin = torch.zeros((2 * batch_size, h, w, packing.KPAD), dtype=torch.bfloat16, device=dev)
-        concat = torch.cat((uc["concat"], cond["concat"]), 0).float().contiguous()
+        self.xin = torch.zeros((self.rows, h, w, packing.KPAD), dtype=torch.bfloat16, device=dev)
+        concat = (torch.cat((uc["concat"], cond["concat"]), 0) if self.pair else cond["concat"]).float().contiguous()
         ops.nhwc_set_channels(concat, self.xin, 4)                         # channels 4..8: mask, masked latent
-        self._emb_cache: Dict[int, torch.Tensor] = {}
+        self._emb_cache: Dict[float, torch.Tensor] = {}
         self.dev = dev
         # stream-K workspaces owned by this stepper (one per launch stream): allocated with it, referenced by the
         # graphs captured from it, freed with it
@@ -240,47 +327,54 @@ class _Stepper:
         # conditioning AND its noise search under launch_context(cu_share=n)); _GraphedSteps overrides it for its runner
         self.cu_share = max(1, int(ops._ctx.cu_share))
 
-    def quantise(self, sigma: float):
-        idx = int((self.table - sigma).abs().argmin())
-        return idx, float(self.table[idx])
+    def coefs(self, sigma: float) -> Precond:
+        """(c_skip, c_out, c_in, c_noise) of the engine's denoiser at the host sigma"""
+        return precond_coefs(self.den, sigma, self.table)
 
-    def emb_rows(self, idx: int) -> torch.Tensor:
-        rows = self._emb_cache.get(idx)
+    def emb_rows(self, c_noise: float) -> torch.Tensor:
+        """the time-embedding rows of the network's timestep input (a table index or a real c_noise), cached by its value"""
+        c_noise = float(c_noise)
+        rows = self._emb_cache.get(c_noise)
         if rows is None:
-            t = torch.full((2 * self.B,), float(idx), dtype=torch.float32, device=self.dev)
+            t = torch.full((self.rows,), c_noise, dtype=torch.float32, device=self.dev)
             rows = self.unet.time_embedding_rows(t)
-            self._emb_cache[idx] = rows
+            self._emb_cache[c_noise] = rows
         return rows
 
     def unet_eps(self, x: torch.Tensor, sigma: float, emit_maps: bool = False, churn: float = 0.0,
                  noise: Optional[torch.Tensor] = None):
-        """the CFG pair's UNet call on x (fp32 NCHW [B,4,h,w]) at the quantised sigma -> (eps fp32 NHWC [2B,h,w,ld],
-        quantised sigma); churn != 0: x += churn * noise first, in the same launch that packs the UNet input"""
-        idx, sq = self.quantise(sigma)
-        c_in = 1.0 / (sq * sq + 1.0) ** 0.5
-        if churn != 0.0:
-            if noise is None:
-                raise ValueError("a churned evaluation needs the step's draw (draw_step_noise)")
-            ops.unet_input_churn(x, noise, self.xin, c_in, churn)
+        """the UNet call on x (fp32 NCHW [B,4,h,w]) at the denoiser's (possibly quantised) sigma -> (network output fp32 NHWC
+        [rows,h,w,ld] — the CFG pair's 2B rows or, unguided, B —, the evaluation's ``Precond``); churn != 0: x += churn * noise
+        first, in the same launch that packs the UNet input"""
+        k = self.coefs(sigma)
+        if churn != 0.0 and noise is None:
+            raise ValueError("a churned evaluation needs the step's draw (draw_step_noise)")
+        if not self.eps_cfg:
+            ops.precond_unet_input(x, self.xin, k.c_in, self.pair, noise if churn != 0.0 else None, churn)
+        elif churn != 0.0:
+            ops.unet_input_churn(x, noise, self.xin, k.c_in, churn)
         else:
-            ops.unet_input(x, self.xin, c_in)
+            ops.unet_input(x, self.xin, k.c_in)
         if emit_maps:
             self.unet.clear_attn_map()
-        emb = self.emb_rows(idx)
+        emb = self.emb_rows(k.c_noise)
         if self.dual and not emit_maps:
             eps = self._forward_two_streams(emb)
         else:
             with ops.launch_context(cu_share=self.cu_share, workspace=self.ws):
                 eps = self.unet.forward_nhwc(self.xin, emb, self.t_kv, emit_maps=emit_maps,
                                              zero_ctx_rows=self.zero_ctx_rows, t_fused=self.t_fused)
-        return eps, sq
+        return eps, k
 
     def step(self, x: torch.Tensor, sigma: float, sigma_next: float, emit_maps: bool = False,
              denoised: Optional[torch.Tensor] = None, churn: float = 0.0, noise: Optional[torch.Tensor] = None) -> None:
         """in-place Euler update of x (fp32 NCHW [B,4,h,w]) from sigma (sigma_hat on a churned step: x += churn * noise before
         the evaluation) to sigma_next; denoised (optional): receives the guided denoised latent"""
-        eps, sq = self.unet_eps(x, sigma, emit_maps, churn, noise)
-        ops.cfg_euler_step(x, eps, sigma, sigma_next, self.scale, denoised=denoised, c_out=-sq)
+        eps, k = self.unet_eps(x, sigma, emit_maps, churn, noise)
+        if self.eps_cfg:
+            ops.cfg_euler_step(x, eps, sigma, sigma_next, self.scale, denoised=denoised, c_out=k.c_out)
+        else:
+            ops.precond_euler_step(x, eps, k.c_skip, k.c_out, sigma, sigma_next, self.scale, self.pair, denoised=denoised)
 
     def run_plan(self, bufs: Dict[str, torch.Tensor], plan, noise: Optional[torch.Tensor] = None) -> None:
         """one sampler step: per evaluation of ``plan`` (a tuple of ``EulerEval`` / ``Eval`` / ``MultistepEval``), the UNet call
@@ -292,16 +386,22 @@ class _Stepper:
                 self.step(src, e.sigma, e.sigma_next, churn=e.churn, noise=noise)
                 continue
             if isinstance(e, MultistepEval):
-                eps, sq = self.unet_eps(src, e.sigma)
-                ops.cfg_multistep_step(src, eps, -sq, self.scale, e.sigma, (e.k0,) + tuple(k for _, k in e.hist),
-                                       hist=[bufs[b] for b, _ in e.hist], d_out=bufs[e.d_out], out=bufs[e.out])
+                eps, k = self.unet_eps(src, e.sigma)
+                ms = dict(hist=[bufs[b] for b, _ in e.hist], d_out=bufs[e.d_out], out=bufs[e.out])
+                ks = (e.k0,) + tuple(kj for _, kj in e.hist)
+                if self.eps_cfg:
+                    ops.cfg_multistep_step(src, eps, k.c_out, self.scale, e.sigma, ks, **ms)
+                else:
+                    ops.precond_multistep_step(src, eps, k.c_skip, k.c_out, self.scale, self.pair, e.sigma, ks, **ms)
                 continue
-            eps, sq = self.unet_eps(src, e.sigma, churn=e.churn, noise=noise)
-            ops.cfg_sampler_step(src, eps, -sq, self.scale, e.kx, e.kd,
-                                 aux=bufs[e.aux] if e.aux else None, ka=e.ka,
-                                 prev=bufs[e.prev] if e.prev else None, kp=e.kp,
-                                 noise=noise if e.kn != 0.0 else None, kn=e.kn,
-                                 out=bufs[e.out], denoised=bufs[e.den_out] if e.den_out else None)
+            eps, k = self.unet_eps(src, e.sigma, churn=e.churn, noise=noise)
+            terms = dict(aux=bufs[e.aux] if e.aux else None, ka=e.ka, prev=bufs[e.prev] if e.prev else None, kp=e.kp,
+                         noise=noise if e.kn != 0.0 else None, kn=e.kn, out=bufs[e.out],
+                         denoised=bufs[e.den_out] if e.den_out else None)
+            if self.eps_cfg:
+                ops.cfg_sampler_step(src, eps, k.c_out, self.scale, e.kx, e.kd, **terms)
+            else:
+                ops.precond_sampler_step(src, eps, k.c_skip, k.c_out, self.scale, self.pair, e.kx, e.kd, **terms)
 
     def check(self) -> None:
         """synchronise and raise if a stream-K launch of this stepper timed out (library err word)"""
@@ -339,11 +439,11 @@ class _GraphedSteps:
     A runner serves one sequence of ``plans`` ((step, plan) pairs; by default Euler over every step of ``sig``), one
     graph per step index."""
 
-    def __init__(self, model, cond, uc, batch_size, latent_hw, scale, sig, cu_share: int = 1, plans=None):
+    def __init__(self, model, cond, uc, batch_size, latent_hw, scale, sig, cu_share: int = 1, plans=None, pair: bool = True):
         # cu_share > 1: this runner is one of several batches in flight; its launches are planned for 1/cu_share of
         # the CUs and its UNet stays on one stream (the concurrency comes from the other batches)
         self.cu_share = int(cu_share)
-        self.st = _Stepper(model, cond, uc, batch_size, latent_hw, scale, two_streams=None if cu_share == 1 else False)
+        self.st = _Stepper(model, cond, uc, batch_size, latent_hw, scale, two_streams=None if cu_share == 1 else False, pair=pair)
         self.st.cu_share = self.cu_share
         self.fingerprint = weights_fingerprint(model)
         if plans is None:
@@ -366,15 +466,15 @@ class _GraphedSteps:
     def rebind(self, cond, uc) -> bool:
         """refresh the static conditioning buffers for a new batch; False if the launch sequence would differ"""
         st = self.st
-        zero_rows = st.B if _all_zero(uc["t_crossattn"]) else 0
+        zero_rows = st.B if st.pair and _all_zero(uc["t_crossattn"]) else 0
         if zero_rows != st.zero_ctx_rows or cond["concat"].shape[0] != st.B:
             return False
-        ctx = torch.cat((uc["t_crossattn"], cond["t_crossattn"]), 0)
+        ctx = torch.cat((uc["t_crossattn"], cond["t_crossattn"]), 0) if st.pair else cond["t_crossattn"]
         for dst_list, src_list in zip(st.t_kv, st.unet.project_context(ctx)):
             for dst, src in zip(dst_list, src_list):
                 dst.copy_(src)
         st.unet.prepare_fused_tattn(st.t_kv, out=st.t_fused)              # tables refreshed in place (views stay valid)
-        concat = torch.cat((uc["concat"], cond["concat"]), 0).float().contiguous()
+        concat = (torch.cat((uc["concat"], cond["concat"]), 0) if st.pair else cond["concat"]).float().contiguous()
         ops.nhwc_set_channels(concat, st.xin, 4)
         return True
 
@@ -388,7 +488,7 @@ class _GraphedSteps:
         st, plan = self.st, self.plans[i]
         noise = self.noise[self.slots[i]] if i in self.slots else None
         for e in plan:
-            st.emb_rows(st.quantise(e.sigma)[0])             # time-embedding rows are cached outside the graph
+            st.emb_rows(st.coefs(e.sigma).c_noise)           # time-embedding rows are cached outside the graph
         if not self.warm:
             # one eager pass on the capture stream: sets kernel attributes, allocates the library's pages
             torch.cuda.synchronize()
@@ -420,7 +520,8 @@ class _GraphedSteps:
 
 class _RunnerKey(NamedTuple):
     """what a cached graph runner was built for: engine, latent shape, guidance scale, device, the exact plan sequence (schedule
-    and init_step) and, on the lanes, its slot of n_lanes"""
+    and init_step), on the lanes its slot of n_lanes, the guider kind and the denoiser's parameterisation (``denoiser_key``: the
+    graphs bake in the host coefficients, so a swapped ``engine.denoiser`` gets a runner of its own)"""
     model: int
     shape: tuple
     scale: float
@@ -428,6 +529,8 @@ class _RunnerKey(NamedTuple):
     plans: tuple
     slot: int = 0
     n_lanes: int = 1
+    guider: str = "VanillaCFG"
+    denoiser: tuple = ()
 
 
 class _PlanSampler:
@@ -449,9 +552,31 @@ class _PlanSampler:
         n = self.num_steps if num_steps is None else num_steps
         return [float(s) for s in self.discretization(n, device="cpu")]
 
-    def _check_fast_path(self):
-        if not isinstance(self.guider, VanillaCFG):
-            raise NotImplementedError("the fused MI355X step implements VanillaCFG guidance")
+    @property
+    def _pair(self) -> bool:
+        """does the guider run the CFG pair (VanillaCFG) or the conditional rows alone (IdentityGuider)?"""
+        return type(self.guider) is VanillaCFG
+
+    @property
+    def _scale(self) -> float:
+        return float(self.guider.scale) if self._pair else 0.0
+
+    def _check_fast_path(self, model=None):
+        """raise for what the fused step does not compute, so that nothing falls through to another formula; ``model``: the engine
+        (its denoiser and scaling classes are checked too)"""
+        if type(self.guider) not in (VanillaCFG, IdentityGuider):
+            raise NotImplementedError(f"the fused MI355X step implements VanillaCFG and IdentityGuider guidance, not "
+                                      f"{type(self.guider).__name__}")
+        if self._pair and type(self.guider.dyn_thresh) is not NoDynamicThresholding:
+            raise NotImplementedError(f"the fused MI355X step implements NoDynamicThresholding, not "
+                                      f"{type(self.guider.dyn_thresh).__name__}")
+        if model is not None:
+            check_denoiser(model.denoiser)
+        elif not self._pair:
+            # the VanillaCFG check is a check of the sampler's own options and has always run without an engine; the unguided route
+            # is one of the udt_precond_* routes, whose scalars come from the engine's denoiser: there is nothing to run it on
+            raise NotImplementedError("IdentityGuider samples through the engine's denoiser (udt_precond_* launches) and no engine "
+                                      "was given; only the VanillaCFG options can be checked without one")
         if getattr(self, "s_churn", 0.0) != 0.0 and not self.implements_churn:
             raise NotImplementedError(f"s_churn > 0 (stochastic sampling) is implemented for EulerEDMSampler only, not "
                                       f"{type(self).__name__}")
@@ -475,7 +600,7 @@ class _PlanSampler:
         the per-sample arg-min is kept (identical to the reference for batch 1; the reference is undefined for
         larger batches).  All randn draws come from the CPU default generator, in the reference's order (churn draws of
         EulerEDMSampler(s_churn > 0) included: the order of the reference run on the CPU)."""
-        self._check_fast_path()
+        self._check_fast_path(model)
         H, W = batch["target_size_as_tuple"][0]
         shape = (cfgs.batch_size, cfgs.channel, int(H) // cfgs.factor, int(W) // cfgs.factor)
         dev = cond["concat"].device
@@ -509,14 +634,14 @@ class _PlanSampler:
             g = len(chunk)
             stepper = steppers.get(g)
             if stepper is None:
-                stepper = steppers[g] = _Stepper(model, tile(cond, g), tile(uc, g), g * B, shape[2:], self.guider.scale)
+                stepper = steppers[g] = _Stepper(model, tile(cond, g), tile(uc, g), g * B, shape[2:], self._scale, pair=self._pair)
             x = torch.cat(chunk, 0).clone()
             x *= (1.0 + sig[0] ** 2.0) ** 0.5
             ll = None
             for i, (e,) in plans:
                 nz = torch.cat([c[slots[i]] for c in churn[g0:g0 + G]], 0) if i in slots else None
                 stepper.step(x, e.sigma, e.sigma_next, emit_maps=True, churn=e.churn, noise=nz)
-                ll = model.loss_fn.get_min_local_loss(stepper.unet.attn_map_cache, mask, seg, cond_only=True)
+                ll = model.loss_fn.get_min_local_loss(stepper.unet.attn_map_cache, mask, seg, cond_only=self._pair)
             scores.extend(ll.reshape(g, B).unbind(0))
             stepper.unet.clear_attn_map()
             stepper.check()
@@ -539,7 +664,7 @@ class _PlanSampler:
 
     def _sample(self, model, x, cond, uc=None, num_steps=None, init_step=0, noise: Optional[torch.Tensor] = None):
         """the plain sampling loop: hipGraph replay, eager launches if graphs are off or unavailable"""
-        self._check_fast_path()
+        self._check_fast_path(model)
         require_gpu(x, type(self).__name__)
         uc = default(uc, cond)
         sig = self._host_sigmas(num_steps)
@@ -552,7 +677,7 @@ class _PlanSampler:
             out = self._run_graphed(model, x, cond, uc, sig, plans, noise)
             if out is not None:
                 return out
-        stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale)
+        stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self._scale, pair=self._pair)
         bufs = {"x": x}
         for name in plan_buffers(plans):
             bufs[name] = torch.empty_like(x)
@@ -563,7 +688,8 @@ class _PlanSampler:
         return x
 
     def _runner_key(self, model, x, plans, slot: int = 0, n_lanes: int = 1) -> _RunnerKey:
-        return _RunnerKey(id(model), tuple(x.shape), float(self.guider.scale), x.device.index, tuple(plans), slot, n_lanes)
+        return _RunnerKey(id(model), tuple(x.shape), self._scale, x.device.index, tuple(plans), slot, n_lanes,
+                          type(self.guider).__name__, denoiser_key(model.denoiser))
 
     def _run_graphed(self, model, x, cond, uc, sig, plans, noise):
         """replay (capturing on first use) the hipGraphs of this sampling configuration; None -> eager launches"""
@@ -575,7 +701,7 @@ class _PlanSampler:
                 gs = None                                       # weights changed under the captured graphs
             if gs is None or not gs.rebind(cond, uc):
                 cache.clear()                                   # one configuration at a time (each holds a memory pool)
-                gs = _GraphedSteps(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale, sig, plans=plans)
+                gs = _GraphedSteps(model, cond, uc, x.shape[0], x.shape[2:], self._scale, sig, plans=plans, pair=self._pair)
                 cache[key] = gs
             gs.load(x, noise)
             gs.capture()
@@ -610,7 +736,8 @@ class _PlanSampler:
             retired.append(cache.pop(key))
             gs = None
         if gs is None or not gs.rebind(cond, uc):
-            gs = _GraphedSteps(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale, sig, cu_share=n_lanes, plans=plans)
+            gs = _GraphedSteps(model, cond, uc, x.shape[0], x.shape[2:], self._scale, sig, cu_share=n_lanes, plans=plans,
+                               pair=self._pair)
             if key in cache:
                 retired.append(cache.pop(key))
             victims = [k for k in cache if (k.model, k.shape, k.n_lanes) != (key.model, key.shape, key.n_lanes)]
@@ -640,7 +767,7 @@ class _PlanSampler:
         batch's ancestral draws (drawn here when not given)."""
         if n_lanes <= 1 or not self.use_graphs:
             return self._sample(model, x, cond, uc, None, init_step, noise)
-        self._check_fast_path()
+        self._check_fast_path(model)
         require_gpu(x, type(self).__name__)
         uc = default(uc, cond)
         sig = self._host_sigmas(None)
@@ -677,7 +804,7 @@ class _PlanSampler:
             noises = [self.draw_step_noise(x.shape, x.device, None, init_step) for x in xs]
         if n == 1 or not self.use_graphs:
             return [self._sample(model, x, c, u, None, init_step, nz) for x, c, u, nz in zip(xs, conds, ucs, noises)]
-        self._check_fast_path()
+        self._check_fast_path(model)
         sig = self._host_sigmas(None)
         plans = self.plans(sig, init_step)
         runners = []
@@ -747,9 +874,9 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
 
     # --------------------------------------------------------------------------------- attend-and-excite
     def get_c_noise(self, x, model, sigma):
-        """reference sampling.py:224-231: the quantised timestep index of sigma (EpsScaling: c_noise = sigma)"""
-        sigma = model.denoiser.possibly_quantize_sigma(sigma)
-        return model.denoiser.possibly_quantize_c_noise(sigma.reshape(-1))
+        """reference sampling.py:224-231: the network's timestep input at sigma — the denoiser's (possibly quantised) c_noise"""
+        sigma = model.denoiser.possibly_quantize_sigma(sigma).reshape(-1)
+        return model.denoiser.possibly_quantize_c_noise(model.denoiser.scaling(sigma)[3])
 
     def attend_and_excite(self, x, model, sigma, cond, batch, alpha, iter_enabled, thres, max_iter=20):
         """reference sampling.py:233-252: x <- x - alpha * d local_loss / d x, once, or (iter_enabled) until the loss falls to
@@ -767,12 +894,13 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
             # the evaluation's launch sequence depends on the shapes only: captured once per sampler, replayed for every update of
             # every step (the timestep index, latent and conditioning are device data in static buffers)
             runner = getattr(self, "_aae_runner", None)
-            if runner is None or not runner.valid_for(unet, x, *args):
+            key = denoiser_key(model.denoiser)                             # (a swapped denoiser gets a capture of its own)
+            if runner is None or not runner.valid_for(unet, x, *args) or getattr(self, "_aae_key", None) != key:
                 runner = self._aae_runner = None                           # (drop the old pool before the new capture)
                 try:
                     runner = backward.GraphedLocalLossGrad(unet, model.loss_fn, x, *args)
                     runner(x, *args)
-                    self._aae_runner = runner
+                    self._aae_runner, self._aae_key = runner, key
                 except Exception as e:
                     if not _is_capture_failure(e):
                         raise
@@ -806,7 +934,8 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         inter = model.decode_first_stage(denoised) if save_inter else None
         if save_loss:
             ll = model.loss_fn.get_min_local_loss(model.model.diffusion_model.attn_map_cache, batch["mask"], batch["seg_mask"])
-            ll = ll[ll.shape[0] // 2:]
+            if type(self.guider) is VanillaCFG:                            # the conditional half of the pair; unguided: every row
+                ll = ll[ll.shape[0] // 2:]
         else:
             ll = torch.zeros(1)
         if save_attn:                                                      # reference sampling.py:344-346
@@ -840,7 +969,7 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         """``noise``: the run's churn draws (draw_step_noise), drawn here when not given"""
         if not (aae_enabled or detailed):
             return self._sample(model, x, cond, uc, num_steps, init_step, noise)
-        self._check_fast_path()
+        self._check_fast_path(model)
         require_gpu(x, "EulerEDMSampler")
         uc = default(uc, cond)
         if noise is None:
@@ -855,7 +984,7 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         x = x.float().contiguous()
         x *= (1.0 + sig[0] ** 2.0) ** 0.5                                  # in place, like the reference :54
         name = name if name is not None else (batch["name"][0] if batch is not None and "name" in batch else "sample")
-        stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self.guider.scale)
+        stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self._scale, pair=self._pair)
         mid = (len(sig) - 1) // 2
         slot = 0                                                           # the k-th churned step reads draw k
         for i in self.get_sigma_gen(len(sig), init_step=init_step):
@@ -884,7 +1013,7 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         iter_lst = np.linspace(start=5, stop=25, num=6, dtype=np.int32)
         thres_lst = np.linspace(start=-0.5, stop=-0.8, num=6)
         B = x.shape[0]
-        stepper = _Stepper(model, cond, uc, B, x.shape[2:], self.guider.scale)
+        stepper = _Stepper(model, cond, uc, B, x.shape[2:], self._scale, pair=self._pair)
         s_in = x.new_ones([B])
         evals0 = getattr(self, "aae_evaluations", 0)
         inters, local_losses = [], []
@@ -901,7 +1030,7 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
             x = self.attend_and_excite(x, model, s_in * e.sigma, cond, batch, alpha, iter_enabled, thres)
             den = torch.empty_like(x)
             stepper.step(x, e.sigma, e.sigma_next, emit_maps=True, denoised=den)
-            ll = model.loss_fn.get_min_local_loss(stepper.unet.attn_map_cache, batch["mask"], batch["seg_mask"], cond_only=True)
+            ll = model.loss_fn.get_min_local_loss(stepper.unet.attn_map_cache, batch["mask"], batch["seg_mask"], cond_only=self._pair)
             local_losses.append(float(ll.mean()))
             if detailed and i == mid:
                 attn_map = stepper.unet.save_attn_map(save_name=name, tokens=batch["label"][0])
@@ -1050,8 +1179,8 @@ class LinearMultistepSampler(_PlanSampler, BaseDiffusionSampler):
         super().__init__(*args, **kwargs)
         self.order = order
 
-    def _check_fast_path(self):
-        super()._check_fast_path()
+    def _check_fast_path(self, model=None):
+        super()._check_fast_path(model)
         if not 1 <= int(self.order) <= MULTISTEP_MAX_ORDER:
             raise NotImplementedError(f"LinearMultistepSampler order {self.order}: the fused step (udt_cfg_multistep_step) "
                                       f"holds 1..{MULTISTEP_MAX_ORDER} derivatives")

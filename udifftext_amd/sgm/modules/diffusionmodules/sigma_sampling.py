@@ -1,7 +1,15 @@
-"""Training-time sigma sampler; constructed by FullLoss (reference loss.py:23, sigma_sampling.py:16-31)."""
+"""Training-time sigma sampler; constructed by FullLoss (reference loss.py:23, sigma_sampling.py:6-31)."""
 import torch
 
 from ...util import default, instantiate_from_config
+
+
+class EDMSampling:
+    def __init__(self, p_mean=-1.2, p_std=1.2):
+        self.p_mean, self.p_std = p_mean, p_std
+
+    def __call__(self, n_samples, rand=None):
+        return (self.p_mean + self.p_std * default(rand, torch.randn((n_samples,)))).exp()
 
 
 class DiscreteSampling:
