@@ -19,6 +19,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import backward_ref as R
+import sliced_check as S
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 REPORT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "parity_report.txt")
@@ -73,6 +76,11 @@ def test_flash_attention_backward_vs_autograd(env, B, H, N):
     got = env.ops.attention_bwd(qb, o, d_o.bfloat16().contiguous(), H, scale)
     for i, nm in enumerate("qkv"):
         _check(f"attention backward d{nm} B{B} H{H} N{N}", got[..., i * C:(i + 1) * C], ref[..., i * C:(i + 1) * C], TOL_ATTN)
+    ref64, floor, scales = R.attn_ref_emul(qkv.cpu(), d_o.cpu(), H, scale, o=o.float().cpu())   # slice by slice (tests/sliced_check.py)
+    for i, nm in enumerate("qkv"):
+        c = slice(i * C, (i + 1) * C)
+        S.check_sliced(f"attention backward d{nm} B{B} H{H} N{N}", got[..., c], ref64[..., c], floor[..., c], S.attn_slices(B, H, N),
+                       abs_scale=scales["d" + nm])
     assert torch.equal(got, env.ops.attention_bwd(qb, o, d_o.bfloat16().contiguous(), H, scale)), "not deterministic"
 
 
@@ -102,6 +110,11 @@ def test_text_cross_attention_backward_vs_autograd(env, B, H, N, L, use_dp, use_
     got = env.ops.xattention_bwd(kvb[..., :C], kvb[..., C:], probs, d_p if use_dp else None,
                                  d_o.bfloat16().contiguous() if use_do else None, H, scale)
     _check(f"text cross-attention backward B{B} H{H} N{N} L{L} dP{int(use_dp)} dO{int(use_do)}", got, ref, TOL_OP)
+    args = (q.cpu(), kv.cpu(), d_p.cpu() if use_dp else None, d_o.cpu() if use_do else None, H, scale)
+    ref64 = R.xattn_bwd(*args, probs=probs.cpu())           # (on the stored probabilities the kernel reads)
+    S.check_sliced(f"text cross-attention backward B{B} H{H} N{N} L{L} dP{int(use_dp)} dO{int(use_do)}", got, ref64["dq"],
+                   R.xattn_bwd(*args, probs=probs.cpu(), emulate=True)["dq"] - ref64["dq"], S.attn_slices(B, H, N),
+                   abs_scale=ref64["abs"]["dq"])
 
 
 @pytest.mark.parametrize("B,heads,size", [(1, 5, 16), (2, 5, 32), (3, 10, 16)])
@@ -141,6 +154,12 @@ def test_layernorm_backward_vs_autograd(env, rows, C):
     _check(f"LayerNorm backward {rows}x{C}", env.ops.layer_norm_bwd(x.bfloat16(), dy.bfloat16(), gamma, 1e-5), ref, TOL_OP)
     _check(f"LayerNorm backward {rows}x{C} + add", env.ops.layer_norm_bwd(x.bfloat16(), dy.bfloat16(), gamma, 1e-5, add=add.bfloat16()),
            ref + add, TOL_OP)
+    for a in (None, add):
+        ref64, sc = R.ln_bwd(x.cpu(), dy.cpu(), gamma.cpu(), 1e-5, None if a is None else a.cpu())
+        floor = R.ln_bwd(x.cpu(), dy.cpu(), gamma.cpu(), 1e-5, None if a is None else a.cpu(), emulate=True) - ref64
+        S.check_sliced(f"LayerNorm backward {rows}x{C}{'' if a is None else ' + add'}",
+                       env.ops.layer_norm_bwd(x.bfloat16(), dy.bfloat16(), gamma, 1e-5, add=None if a is None else a.bfloat16()), ref64, floor,
+                       S.row_col_slices(rows, C, 4, 512), abs_scale=sc)
 
 
 @pytest.mark.parametrize("B,hw,C,silu", [(2, 16, 320, True), (1, 8, 640, False), (2, 8, 1280, True), (1, 32, 320, False), (1, 64, 320, True),
@@ -169,6 +188,16 @@ def test_groupnorm_backward_vs_autograd(env, B, hw, C, silu):
     finally:
         env.ops.GN_BWD_CHUNKED = True
     _check(f"GroupNorm{'+SiLU' if silu else ''} backward B{B} {hw}x{hw}x{C} + add (one workgroup per group)", got1, ref + add, TOL_OP)
+    flat = lambda t: t.reshape(B, hw * hw, C)
+    cpu = (flat(x).cpu(), flat(dy).cpu(), gamma.cpu(), beta.cpu(), 32, 1e-5, silu)
+    got0 = env.ops.group_norm_bwd(x.bfloat16(), dy.bfloat16(), gamma, beta, 32, 1e-5, silu)
+    for nm, res, a in (("+ add", got, flat(add).cpu()), ("no add", got0, None), ("+ add (one workgroup per group)", got1, flat(add).cpu())):
+        ref64, sc = R.gn_bwd(*cpu, a)
+        floor = R.gn_bwd(*cpu, a, emulate=True) - ref64
+        name = f"GroupNorm{'+SiLU' if silu else ''} backward B{B} {hw}x{hw}x{C} {nm}"
+        S.check_sliced(name + " by (sample, group)", flat(res), ref64, floor, S.gn_group_slices(B, C, 32), abs_scale=sc)
+        S.check_sliced(name + " by apply workgroup", res.reshape(B, -1), ref64.reshape(B, -1), floor.reshape(B, -1),
+                       S.flat_slices(B, hw * hw * C, 8192), abs_scale=sc)
 
 
 def test_geglu_forward_backward_vs_autograd(env):
@@ -183,6 +212,9 @@ def test_geglu_forward_backward_vs_autograd(env):
         (ref,) = torch.autograd.grad((y * dy).sum(), [t])
     _check("GEGLU forward on stored pre-activations", env.ops.geglu(ag.bfloat16()), y.detach(), TOL_OP)
     _check("GEGLU backward", env.ops.geglu_bwd(ag.bfloat16(), dy.bfloat16()), ref, TOL_OP)
+    (rf, rb), (ef, eb) = R.geglu(ag.cpu(), dy.cpu()), R.geglu(ag.cpu(), dy.cpu(), emulate=True)
+    S.check_sliced("GEGLU forward on stored pre-activations", env.ops.geglu(ag.bfloat16()), rf, ef - rf, S.row_col_slices(rows, inner, 1, 2048))
+    S.check_sliced("GEGLU backward", env.ops.geglu_bwd(ag.bfloat16(), dy.bfloat16()), rb, eb - rb, S.row_col_slices(rows, 2 * inner, 1, 2048))
 
 
 def test_backward_data_of_linear_and_convolutions_through_the_forward_kernels(env):
@@ -193,6 +225,9 @@ def test_backward_data_of_linear_and_convolutions_through_the_forward_kernels(en
     lin = H.Linear(320, 1280).to(dev)
     dy = _bf(torch.randn((512, 1280), generator=g)).to(dev)
     _check("linear backward-data", env.bw.linear_bwd(lin, dy.bfloat16()), dy @ lin.weight.float(), TOL_OP)
+    ref64 = dy.double().cpu() @ R.bf(lin.weight.detach().double().cpu())          # (the kernel's operand: the weight as stored, bf16)
+    S.check_sliced("linear backward-data", env.bw.linear_bwd(lin, dy.bfloat16()), ref64, R.bf(ref64) - ref64, S.row_col_slices(512, 320, 32, 64),
+                   abs_scale=R.rms(dy.double().cpu().abs() @ R.bf(lin.weight.detach().double().cpu()).abs()))
     nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous().bfloat16()
     for name, conv, hw_in in (("3x3", H.Conv2d(320, 640, 3, padding=1), 16), ("1x1", H.Conv2d(640, 320, 1), 16),
                               ("3x3 stride 2", H.Conv2d(320, 320, 3, stride=2, padding=1), 32)):
@@ -205,9 +240,18 @@ def test_backward_data_of_linear_and_convolutions_through_the_forward_kernels(en
             (ref,) = torch.autograd.grad((y * dyc).sum(), [t])
         got = env.bw.down_bwd(conv, nhwc(dyc), (hw_in, hw_in)) if conv.stride == 2 else env.bw.conv_bwd(conv, nhwc(dyc))
         _check(f"convolution backward-data {name}", got.float().permute(0, 3, 1, 2), ref, TOL_OP)
+        w64 = R.bf(conv.weight.detach().double().cpu())
+        grad_in = lambda w_, d_: torch.nn.grad.conv2d_input(tuple(x.shape), w_, d_, stride=conv.stride, padding=conv.padding)
+        ref64 = grad_in(w64, dyc.double().cpu()).permute(0, 2, 3, 1).reshape(-1, conv.in_channels)
+        S.check_sliced(f"convolution backward-data {name}", got.reshape(-1, conv.in_channels), ref64, R.bf(ref64) - ref64,
+                       S.row_col_slices(ref64.shape[0], conv.in_channels, 32, 64),
+                       abs_scale=R.rms(grad_in(w64.abs(), dyc.double().cpu().abs())))
     dyu = _bf(torch.randn((2, 32, 32, 320), generator=g)).to(dev)
     ref_u = dyu.reshape(2, 16, 2, 16, 2, 320).sum(dim=(2, 4))
     _check("nearest x2 upsampling backward (2x2 sums)", env.ops.sum2x2(dyu.bfloat16()), ref_u, TOL_OP)
+    ref64, sc = R.sum2x2(dyu.cpu())
+    S.check_sliced("nearest x2 upsampling backward (2x2 sums)", env.ops.sum2x2(dyu.bfloat16()).reshape(-1, 320), ref64.reshape(-1, 320),
+                   (R.sum2x2(dyu.cpu(), emulate=True) - ref64).reshape(-1, 320), S.row_col_slices(512, 320, 32, 64), abs_scale=sc)
 
 
 # ------------------------------------------------------------------------------------------------ the two-block slice vs the oracle

@@ -16,6 +16,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import backward_ref as R
+import sliced_check as S
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 REPORT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "parity_report.txt")
@@ -66,6 +69,8 @@ def test_weight_gradient_kernel_and_the_forward_gemm_on_transposed_operands(env,
     ref = dy.t() @ x
     got = env.ops.weight_grad(dy.bfloat16(), x.bfloat16())
     _check(f"dW = dY^T X {M}x{N}x{K} (udt_wgrad_bf16)", got, ref, TOL_OP)
+    ref64, asum = R.wgrad(dy.cpu(), x.cpu())                # element by element: 16 x 2^-24 x sum|summands| (tests/sliced_check.py)
+    S.check_fp32_sum(f"dW = dY^T X {M}x{N}x{K} (udt_wgrad_bf16)", got, ref64, asum)
     assert torch.equal(got, env.ops.weight_grad(dy.bfloat16(), x.bfloat16())), "fixed summation order: repeatable bit for bit"
     wide_y = torch.zeros((M, N + 64), dtype=torch.bfloat16, device=env.dev); wide_y[:, 8:N + 8] = dy.bfloat16()
     wide_x = torch.zeros((M, 2 * K), dtype=torch.bfloat16, device=env.dev); wide_x[:, K:] = x.bfloat16()
@@ -74,9 +79,11 @@ def test_weight_gradient_kernel_and_the_forward_gemm_on_transposed_operands(env,
         try:
             env.ops.WGRAD_KERNEL = False
             _check(f"dW = dY^T X {M}x{N}x{K} (transposes + forward GEMM)", env.ops.weight_grad(dy.bfloat16(), x.bfloat16()), ref, TOL_OP)
+            S.check_fp32_sum(f"dW = dY^T X {M}x{N}x{K} (transposes + forward GEMM)", env.ops.weight_grad(dy.bfloat16(), x.bfloat16()), ref64, asum)
         finally:
             env.ops.WGRAD_KERNEL = True
     _check(f"bias gradient (column sums) {M}x{N}", env.ops.colsum(dy.bfloat16()), dy.sum(dim=0), TOL_OP)
+    S.check_fp32_sum(f"bias gradient (column sums) {M}x{N}", env.ops.colsum(dy.bfloat16()), *R.colsum(dy.cpu()))
 
 
 @pytest.mark.parametrize("rows,C", [(512, 320), (300, 640), (70, 1280)])
@@ -91,6 +98,9 @@ def test_layernorm_parameter_gradients_vs_autograd(env, rows, C):
     dg, db = env.ops.layer_norm_param_grad(x.bfloat16(), dy.bfloat16(), 1e-5)
     _check(f"LayerNorm d gamma {rows}x{C}", dg, rg, TOL_OP)
     _check(f"LayerNorm d beta {rows}x{C}", db, rb, TOL_OP)
+    dg64, db64, ag, ab = R.ln_param_grad(x.cpu(), dy.cpu(), 1e-5)
+    S.check_fp32_sum(f"LayerNorm d gamma {rows}x{C}", dg, dg64, ag)
+    S.check_fp32_sum(f"LayerNorm d beta {rows}x{C}", db, db64, ab)
 
 
 @pytest.mark.parametrize("B,H,N,L,use_dp,use_do", [(2, 5, 256, 12, True, True), (1, 10, 300, 12, False, True), (2, 5, 70, 4, True, False)])
@@ -121,6 +131,12 @@ def test_text_cross_attention_context_gradients_vs_autograd(env, B, H, N, L, use
         _check(f"text cross-attention dV B{B} H{H} N{N} L{L}", dv, ref[..., C:], TOL_OP)
     else:
         assert not bool(dv.float().abs().max() > 0)
+    args = (q.cpu(), kv.cpu(), d_p.cpu() if use_dp else None, d_o.cpu() if use_do else None, H, scale)
+    ref64 = R.xattn_bwd(*args, probs=probs.cpu())           # (on the stored probabilities the kernel reads)
+    emul = R.xattn_bwd(*args, probs=probs.cpu(), emulate=True)
+    for nm, res in (("dk", dk), ("dv", dv)):
+        S.check_sliced(f"text cross-attention d{nm[1].upper()} B{B} H{H} N{N} L{L}", res, ref64[nm],
+                       emul[nm] - ref64[nm], S.attn_slices(B, H, L), abs_scale=ref64["abs"][nm])
 
 
 @pytest.mark.parametrize("B,heads,size", [(2, 5, 16), (1, 10, 32)])
@@ -159,6 +175,11 @@ def test_eps_prediction_loss_and_its_seed_vs_autograd(env):
     loss, d_eps = env.ops.diff_loss_grad(eps, noised, target, sigma)
     assert torch.allclose(loss, lb.detach(), rtol=1e-5)
     _check("eps-prediction loss seed d loss / d eps", d_eps[..., :4], ref, TOL_OP)
+    coef = (torch.ones(B), -sigma.cpu(), sigma.cpu() ** -2.0)
+    _, ref64, sc = R.precond_loss_grad(eps.cpu(), noised.cpu(), target.cpu(), *coef)
+    floor = R.precond_loss_grad(eps.cpu(), noised.cpu(), target.cpu(), *coef, emulate=True)[1] - ref64
+    S.check_sliced("eps-prediction loss seed d loss / d eps", d_eps[..., :4].reshape(B, -1), ref64.reshape(B, -1), floor.reshape(B, -1),
+                   S.flat_slices(B, h * h * 4, 1024), abs_scale=sc)          # one slice per sample (its workgroup)
     assert not bool(d_eps[..., 4:].any())
 
 
