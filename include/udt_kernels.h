@@ -50,6 +50,11 @@
  *     udt_local_loss_bwd, udt_local_loss_seg_bwd, udt_diff_loss_grad          FullLoss.get_min_local_loss / get_local_loss / __call__
  *     udt_wgrad_bf16, udt_colsum_bf16                     weight / bias gradients of the trained nn.Linear layers
  *     udt_adamw_f32                                       torch.optim.AdamW.step (diffusion.py:49-51,202-222)
+ *     udt_wgrad_bf16_acc, udt_colsum_bf16_acc, udt_ln_param_grad_acc      the same gradients ADDED to their destination: autograd's
+ *                                                         accumulation into .grad across the micro-batches of a window
+ *                                                         (configs/train.yaml:21 accumulate_grad_batches)
+ *     udt_bucket_update_f32, udt_bucket_swap_f32          AdamW.step over every trained tensor + LitEma.forward (sgm/modules/ema.py:33-52),
+ *                                                         LitEma.store / copy_to / restore (ema.py:56-86), one launch each
  *     (backward-data of linears and convolutions: udt_gemm on re-packed weights)
  *
  * Conventions
@@ -593,6 +598,45 @@ int udt_precond_loss_grad(const float* f, const float* noised, const float* targ
 /* torch.optim.AdamW step on fp32 parameters (diffusion.py:49-51,219): g is scaled by grad_scale first (gradient accumulation / world) */
 int udt_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int32_t step, float grad_scale, void* stream);
+/* ---- gradient accumulation and the fused optimiser step (configs/train.yaml:21 accumulate_grad_batches; diffusion.py:75-78,178-195 with
+ * sgm/modules/ema.py).  The trained tensors' gradients live in ONE flat fp32 bucket; the reverse pass adds into it, the collectives
+ * run on it in place, one launch consumes it. ------------------------------------------------------------------------------------- */
+/* udt_wgrad_bf16 with accumulate: accumulate != 0 gives dw += dy^T x, the fixed-order sum formed first and added once (what
+ * torch.autograd does to .grad on the second backward() of a window); accumulate == 0 is udt_wgrad_bf16, bit for bit.  With one row
+ * range (udt_wgrad_splits == 1 after rounding) the add happens in the kernel's epilogue: no temporary of dw's size */
+int udt_wgrad_bf16_acc(const void* dy, const void* x, float* dw, float* partials, int64_t R, int32_t N, int32_t K, int32_t ldy, int32_t ldx,
+                       int32_t accumulate, void* stream);
+/* udt_colsum_bf16 with accumulate: out (+)= column sums (bias gradient, accumulated as above) */
+int udt_colsum_bf16_acc(const void* x, float* partials, float* out, int64_t rows, int32_t C, int32_t accumulate, void* stream);
+/* udt_ln_param_grad with accumulate: dgamma_dbeta [2, C] (+)= (sum_r dy * xhat, sum_r dy) (t_norm's gradients, accumulated as above) */
+int udt_ln_param_grad_acc(const void* x, const void* dy, float* partials, float* dgamma_dbeta, int64_t rows, int32_t C, float eps,
+                          int32_t accumulate, void* stream);
+/* one trained tensor of the bucket: its fp32 parameter p and EMA shadow (n values each; 16-byte aligned pointers take the 16-byte
+ * path, others go element by element), and where its n gradients / moments start in the flat buffers: offset, a multiple of 4 floats */
+typedef struct udt_bucket_segment {
+  float* p;
+  float* shadow;              /* may be NULL when the mode has no EMA bit */
+  int64_t offset;
+  int64_t n;
+} udt_bucket_segment;
+/* elements per chunk of the chunk map below */
+#define UDT_BUCKET_CHUNK 4096
+#define UDT_BUCKET_ADAMW 1
+#define UDT_BUCKET_EMA 2
+/* The optimiser step over all segments in one launch.  segments: DEVICE table; chunk_map: DEVICE int32 [n_chunks, 2] = (segment,
+ * chunk index inside it), every segment cut into ceil(n / UDT_BUCKET_CHUNK) chunks, in any order, each chunk once.  g / m / v: the
+ * flat fp32 gradient bucket and AdamW moments (16-byte aligned; NULL allowed without the AdamW bit).  mode:
+ *   UDT_BUCKET_ADAMW   p, m, v <- torch.optim.AdamW.step with gradient g * grad_scale: the arithmetic of udt_adamw_f32 (diffusion.py:49-51,
+ *                      219; grad_scale = 1 / (accumulate_grad_batches * world))
+ *   UDT_BUCKET_EMA     shadow -= one_minus_decay * (shadow - p): LitEma.forward (ema.py:40-52; the host computes the decay, ema.py:36-38)
+ *   both               AdamW first, then the EMA on the updated p: optimizer.step() then on_train_batch_end (diffusion.py:178-180)
+ * Elements between the segments (padding) are neither read nor written; g is only read. */
+int udt_bucket_update_f32(const udt_bucket_segment* segments, const int32_t* chunk_map, int32_t n_chunks, float* g, float* m, float* v,
+                          int32_t mode, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale,
+                          float one_minus_decay, void* stream);
+/* p <-> shadow over the same table and map: LitEma.store + copy_to entering ema_scope, restore leaving it (ema.py:56-86,
+ * diffusion.py:182-195); its own inverse */
+int udt_bucket_swap_f32(const udt_bucket_segment* segments, const int32_t* chunk_map, int32_t n_chunks, void* stream);
 /* x fp32 += a * y fp32: the attend-and-excite update x <- x - alpha * grad (sampling.py:247) */
 int udt_axpy_f32(float* x, const float* y, float a, int64_t n, void* stream);
 /* x bf16 += y bf16 (n elements, n % 8 == 0) ; utility for residuals outside GEMM epilogues */

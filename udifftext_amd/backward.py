@@ -125,8 +125,8 @@ def transformer_block_fwd(blk, t1: torch.Tensor, B: int, kv: torch.Tensor, rec: 
         kv_c = kv
     kk, vv, vv_c = kv_c[..., :Cc], kv[..., Cc:], kv_c[..., Cc:]
     o2 = ops.xattention(q, kk, vv, ta.heads, ta.dim_head, ta.scale, probs=probs)
-    # ``pgrads``: set to a dict before the reverse pass to ALSO collect the gradients of this block's trainable parameters (the
-    # reference trains t_attn / t_norm only, configs/train/textdesign_sd_2.yaml:4-6), keyed by their state-dict names below ``name``;
+    # ``pgrads``: set to a sink (_DictSink / _BucketSink) before the reverse pass to ALSO collect the gradients of this block's trainable
+    # parameters (the reference trains t_attn / t_norm only, configs/train/textdesign_sd_2.yaml:4-6), keyed by their state-dict names below ``name``;
     # ``ctx`` / ``ctx_c``: the context rows [B * L, Dc] (plain / centred) behind kv, needed for d to_k / d to_v
     item = {"name": name, "heads": ta.heads, "size": int(N ** 0.5), "hw": map_hw(N, hw), "attn_map": probs, "d_probs": None, "pgrads": None,
             "ctx": None, "ctx_c": None, "block": blk}
@@ -138,27 +138,27 @@ def transformer_block_fwd(blk, t1: torch.Tensor, B: int, kv: torch.Tensor, rec: 
     t4 = ff.net[2](ops.geglu(ag), residual=t3)
     del n1, n2, n3
 
-    def param_grads(pg: dict, d_t3, d_o2, dq, d_n2, dP):
-        """gradients of t_attn.{to_q, to_k, to_v, to_out.0} and t_norm (fp32, state-dict names)"""
+    def param_grads(sink, d_t3, d_o2, dq, d_n2, dP):
+        """gradients of t_attn.{to_q, to_k, to_v, to_out.0} and t_norm (fp32, state-dict names), handed to ``sink``: a _DictSink
+        stores each as a new tensor, a _BucketSink ADDS each to its view of the gradient bucket — ONE body for both routes"""
         pre = name + "."                                            # "...transformer_blocks.i.t_attn."
         nrm = name[:-len("t_attn")] + "t_norm."
         if d_t3 is not None:                                        # t3 = o2 W_out^T + b + t2
-            pg[pre + "to_out.0.weight"] = ops.weight_grad(d_t3, o2.reshape(M, Cc))
-            pg[pre + "to_out.0.bias"] = ops.colsum(d_t3)
+            sink.weight_grad(pre + "to_out.0.weight", d_t3, o2.reshape(M, Cc))
+            sink.colsum(pre + "to_out.0.bias", d_t3)
         else:
-            pg[pre + "to_out.0.weight"] = torch.zeros((Cc, Cc), dtype=torch.float32, device=t1.device)
-            pg[pre + "to_out.0.bias"] = torch.zeros((Cc,), dtype=torch.float32, device=t1.device)
+            sink.zero(pre + "to_out.0.weight", (Cc, Cc), t1.device)
+            sink.zero(pre + "to_out.0.bias", (Cc,), t1.device)
         n2r = ops.layer_norm(t2, blk.t_norm.weight, blk.t_norm.bias, blk.t_norm.eps)
-        pg[pre + "to_q.weight"] = ops.weight_grad(dq.reshape(M, Cc), n2r)
+        sink.weight_grad(pre + "to_q.weight", dq.reshape(M, Cc), n2r)
         dk, dv = ops.xattention_bwd_kv(q, vv_c, probs, dP, d_o2, ta.heads, ta.scale)
         Lc = kv.shape[1]
         cx = item["ctx"]
         cxc = item["ctx_c"] if item["ctx_c"] is not None else cx
         # (sum_l dK_l = 0: the centred rows give the same product, without the cancellation of the tokens' common part)
-        pg[pre + "to_k.weight"] = ops.weight_grad(dk.reshape(B * Lc, Cc), cxc)
-        pg[pre + "to_v.weight"] = ops.weight_grad(dv.reshape(B * Lc, Cc), cx)
-        dg, db = ops.layer_norm_param_grad(t2, d_n2, blk.t_norm.eps)
-        pg[nrm + "weight"], pg[nrm + "bias"] = dg, db
+        sink.weight_grad(pre + "to_k.weight", dk.reshape(B * Lc, Cc), cxc)
+        sink.weight_grad(pre + "to_v.weight", dv.reshape(B * Lc, Cc), cx)
+        sink.layer_norm_param_grad(nrm + "weight", nrm + "bias", t2, d_n2, blk.t_norm.eps)
 
     def bwd(d_t4):
         dP = item["d_probs"]
@@ -261,6 +261,56 @@ def _acc(a: Optional[torch.Tensor], b: Optional[torch.Tensor]) -> Optional[torch
     return ops.add_(a.contiguous(), b.contiguous())
 
 
+class _DictSink:
+    """the tape's parameter gradients as new tensors in a dict, under the tape's names (the blocks the pass never reaches: zeros)"""
+
+    def __init__(self, grads: dict):
+        self.grads = grads
+
+    def weight_grad(self, key: str, dy: torch.Tensor, x: torch.Tensor) -> None:
+        self.grads[key] = ops.weight_grad(dy, x)
+
+    def colsum(self, key: str, x: torch.Tensor) -> None:
+        self.grads[key] = ops.colsum(x)
+
+    def layer_norm_param_grad(self, key_w: str, key_b: str, x: torch.Tensor, dy: torch.Tensor, eps: float) -> None:
+        self.grads[key_w], self.grads[key_b] = ops.layer_norm_param_grad(x, dy, eps)
+
+    def zero(self, key: str, shape, device) -> None:
+        self.grads[key] = torch.zeros(shape, dtype=torch.float32, device=device)
+
+
+class _BucketSink:
+    """the same gradients ADDED to the views of a gradient bucket (udifftext_amd.training.GradBucket: ``views`` = {state-dict name:
+    fp32 view of one flat buffer}) through the udt_*_acc entry points: a window of micro-batches accumulates there as torch.autograd
+    accumulates into .grad; what the dict route sets to zero adds nothing"""
+
+    def __init__(self, bucket, prefix: str):
+        self.bucket, self.prefix = bucket, prefix
+
+    def view(self, key: str) -> torch.Tensor:
+        return self.bucket.views[self.prefix + key]
+
+    def weight_grad(self, key: str, dy: torch.Tensor, x: torch.Tensor) -> None:
+        ops.weight_grad(dy, x, out=self.view(key))
+
+    def colsum(self, key: str, x: torch.Tensor) -> None:
+        ops.colsum(x, out=self.view(key))
+
+    def layer_norm_param_grad(self, key_w: str, key_b: str, x: torch.Tensor, dy: torch.Tensor, eps: float) -> None:
+        a, b = self.view(key_w), self.view(key_b)
+        if a.dim() == 1 and a.shape == b.shape and b.data_ptr() == a.data_ptr() + 4 * a.numel():
+            o = self.bucket.offsets[self.prefix + key_w]             # neighbours in the bucket: ONE [2, C] destination
+            ops.layer_norm_param_grad(x, dy, eps, out=self.bucket.flat[o:o + 2 * a.numel()].view(2, a.numel()))
+            return
+        dg, db = ops.layer_norm_param_grad(x, dy, eps)
+        ops.axpy_(a, dg.contiguous(), 1.0)
+        ops.axpy_(b, db.contiguous(), 1.0)
+
+    def zero(self, key: str, shape, device) -> None:
+        pass
+
+
 class UNetTape:
     """Tape-mode forward of the UNet (every block through the ``*_fwd`` functions above) that can be reversed:
         tape = UNetTape(unet, xin, timesteps, t_context, with_head=...)      # xin: bf16 NHWC [B, h, w, CPAD]
@@ -268,7 +318,8 @@ class UNetTape:
         tape.eps          fp32 NHWC [B, h, w, 4] when with_head (out.0 GroupNorm + SiLU, out.2 convolution), else None
         tape.backward(d_eps=None, param_grads=None) -> d xin (bf16 NHWC)     # d_eps: bf16 NHWC [B, h, w, 64] cotangent of eps;
                           map cotangents are whatever the caller stored in maps[i]["d_probs"]; param_grads: a dict that receives the
-                          fp32 gradients of the t_attn / t_norm parameters under their state-dict names (prefix ``param_prefix``)"""
+                          fp32 gradients of the t_attn / t_norm parameters under their state-dict names (prefix ``param_prefix``),
+                          or a training.GradBucket whose views they are added to"""
 
     def __init__(self, unet, xin: torch.Tensor, timesteps: torch.Tensor, t_context: torch.Tensor, with_head: bool = False,
                  param_prefix: str = "model.diffusion_model."):
@@ -307,9 +358,17 @@ class UNetTape:
             self.eps = ops.conv2d(a, w, bb, ksize=3, flags=ops.L.GEMM_OUT_F32, n_out=w.shape[0])
             self._head = (h, gn, conv)
 
-    def backward(self, d_eps: Optional[torch.Tensor] = None, param_grads: Optional[dict] = None):
+    def backward(self, d_eps: Optional[torch.Tensor] = None, param_grads=None):
+        """``param_grads``: a dict (receives one new tensor per trained parameter, zeros for the blocks the pass never reaches), or a
+        gradient bucket (training.GradBucket): the gradients are ADDED to its views and unreached blocks add nothing — the caller
+        starts a window of micro-batches from ``zero_()``"""
+        from .training import GradBucket                               # (training imports this module)
+        into_bucket = isinstance(param_grads, GradBucket)
+        sink = None
+        if param_grads is not None:
+            sink = _BucketSink(param_grads, self.prefix) if into_bucket else _DictSink(param_grads)
         for it in self.maps:
-            it["pgrads"] = param_grads
+            it["pgrads"] = sink
         d = None
         if d_eps is not None:
             h, gn, conv = self._head
@@ -324,7 +383,7 @@ class UNetTape:
         for i in reversed(range(n_in)):
             d = _acc(d, d_skips[i])
             d, _ = self.tape[i](d)
-        if param_grads is not None:
+        if param_grads is not None and not into_bucket:
             # blocks the reverse pass never reached (downstream of the last map read, no eps cotangent) have zero gradients
             for it in self.maps:
                 blk = it["block"]

@@ -1003,14 +1003,14 @@ __global__ void __launch_bounds__(256) colsum_partial_kernel(const uint16_t* __r
 // TRANSPOSED ([column][row], 16-bit stores, rows xor-swizzled in groups of eight against bank conflicts), from where the fragments are
 // plain 16-byte reads; the next step's global loads are in flight during the MFMAs.  grid (tiles_k, tiles_n, S): the rows are cut
 // into S ranges whose fp32 partial tiles go to `part` [S][N][K] and are added in range order by reduce_rows_f32_kernel (S = 1:
-// straight to dW).  Replaces transpose x 2 + the forward GEMM with fp32 output (1280 launches of 8 us + 132 us per large one).
+// straight to dW; `accumulate`: dW += the tile in the epilogue).  Replaces transpose x 2 + the forward GEMM with fp32 output (1280 launches of 8 us + 132 us per large one).
 constexpr int WG_RS = 32;          // rows per step
 constexpr int WG_P = 32;           // LDS pitch (elements) of a transposed row: 64 B, no padding — the swizzle spreads the banks
 
 UDT_DEVINL int wg_pos(int col, int r) { return col * WG_P + ((((r >> 3) ^ (col >> 3)) & 3) << 3) + (r & 7); }
 
 __global__ void __launch_bounds__(256) wgrad_kernel(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ x, float* __restrict__ out,
-                                                    int R, int N, int K, int ldy, int ldx, int rows_per_split) {
+                                                    int R, int N, int K, int ldy, int ldx, int rows_per_split, int accumulate) {
   __shared__ __attribute__((aligned(16))) uint16_t yt[128 * WG_P];
   __shared__ __attribute__((aligned(16))) uint16_t xt[128 * WG_P];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
@@ -1087,7 +1087,10 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const uint16_t* __restrict__
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int nn = n0 + wn + a * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
-        if (nn < N && kk < K) dst[(long long)nn * K + kk] = acc[a][b][r];
+        if (nn < N && kk < K) {                                 // (accumulate: S = 1 only — dW += the finished sum, no temporary)
+          float* d = dst + (long long)nn * K + kk;
+          *d = accumulate ? *d + acc[a][b][r] : acc[a][b][r];
+        }
       }
     }
 }
@@ -1387,20 +1390,147 @@ __global__ void __launch_bounds__(256) precond_loss_grad_kernel(const float* __r
   if (threadIdx.x == 0) loss[b] = tot / (4.0f * (float)hw);
 }
 
-// torch.optim.AdamW (the reference's default optimizer, diffusion.py:49-51): decoupled weight decay, bias-corrected moments
+// torch.optim.AdamW (the reference's default optimizer, diffusion.py:49-51): decoupled weight decay, bias-corrected moments.
+// ONE statement of the element update, shared by the per-tensor kernel and the bucket kernel (the same expression tree in both)
+struct AdamwCoefs { float lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale; };
+
+UDT_DEVINL void adamw_element(float& p, float g, float& m, float& v, const AdamwCoefs& k) {
+  // PINNED ROUNDING — do not "simplify" this back to plain expressions, and do not re-derive it from a newer compiler's output.
+  // Contraction is off and every fused multiply-add is written out, so each kernel that inlines this function rounds alike:
+  //   1 - lr * wd            = fma(-lr, wd, 1)                  one rounding
+  //   m' = b1 m + (1 - b1) g = fma(1 - b1, g, b1 * m)           b1 * m rounded, the other product fused
+  //   v' = b2 v + (1 - b2) g g = (b2 * v) + (((1 - b2) * g) * g)  three roundings and an add, NO fma
+  //   update                 = ((lr / bc1) * m') / (sqrt(v') / bc2_sqrt + eps), IEEE divisions and sqrt, then a plain subtraction
+  // These are the fusions hipcc (ROCm 7) chose for adamw_kernel when the arithmetic stood inline there, so udt_adamw_f32 computes what
+  // it always computed; and they are written out because, left to the compiler, the bucket kernel's 16-byte path fused OTHER
+  // products of the same source (m and v came out 1 ulp apart).  Which products a compiler fuses is its choice and changes between
+  // releases; trained weights and the bit-equality of the two optimiser routes (tests/test_optim_gpu.py) must not change with it.
+#pragma clang fp contract(off)
+  const float gi = g * k.gscale;
+  float pi = p * __builtin_fmaf(-k.lr, k.wd, 1.0f);
+  const float mi = __builtin_fmaf(1.0f - k.b1, gi, k.b1 * m);
+  const float vi = k.b2 * v + ((1.0f - k.b2) * gi) * gi;
+  m = mi;
+  v = vi;
+  pi = pi - ((k.lr / k.bc1) * mi) / (sqrtf(vi) / k.bc2_sqrt + k.eps);
+  p = pi;
+}
+
 __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, long long n, float lr, float b1, float b2, float eps, float wd,
                                                     float bc1, float bc2_sqrt, float gscale) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float gi = g[i] * gscale;
-  float pi = p[i] * (1.0f - lr * wd);
-  const float mi = b1 * m[i] + (1.0f - b1) * gi;
-  const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-  m[i] = mi;
-  v[i] = vi;
-  pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
-  p[i] = pi;
+  const AdamwCoefs k = {lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale};
+  adamw_element(p[i], g[i], m[i], v[i], k);
+}
+
+// ---- the fused bucket optimiser step: ONE launch over every trained tensor (112 of them, 75.9 M values).  The gradients live in one
+// flat fp32 bucket g (training.GradBucket), the moments m / v in flat buffers of the same layout; segment s of the device table is
+// tensor s: its parameter p, its EMA shadow (LitEma, sgm/modules/ema.py), its offset in the flat buffers (a multiple of 4 floats) and
+// its length.  Work is cut into chunks of UDT_BUCKET_CHUNK elements that never cross a segment; chunk_map[c] = (segment, chunk index
+// inside it) is precomputed on the host: no per-element search, and a 1280 x 1280 tensor is 400 chunks.  A workgroup takes chunks
+// grid-strided; a thread takes 4 float4 per chunk (16-byte loads / stores of p, shadow, g, m, v) when p and shadow are 16-byte
+// aligned, the ragged end of the segment and unaligned segments go element by element.  The padding between segments is neither
+// read nor written.  MODE bit 0: AdamW (adamw_element); bit 1: EMA shadow -= one_minus_decay * (shadow - p) (ema.py:50-52) on the
+// UPDATED p.
+struct BucketSegment { float* p; float* shadow; long long offset; long long n; };
+typedef __attribute__((address_space(1))) float gfloat;
+typedef __attribute__((address_space(1))) f32x4 gf32x4;
+constexpr int BK_CHUNK = 4096;
+static_assert(BK_CHUNK == UDT_BUCKET_CHUNK, "include/udt_kernels.h states the chunk size the host builds the map for");
+
+template <int MODE>
+UDT_DEVINL void bucket_element(float& p, float& sh, float g, float& m, float& v, const AdamwCoefs& k, float omd) {
+  if (MODE & 1) adamw_element(p, g, m, v, k);
+  if (MODE & 2) sh -= omd * (sh - p);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) bucket_update_kernel(const BucketSegment* __restrict__ segs, const int* __restrict__ chunk_map,
+                                                            int n_chunks, float* __restrict__ gflat, float* __restrict__ mflat,
+                                                            float* __restrict__ vflat, AdamwCoefs k, float omd) {
+  constexpr bool AD = (MODE & 1) != 0, EM = (MODE & 2) != 0;
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const BucketSegment sg = segs[chunk_map[2 * c]];
+    const long long start = (long long)chunk_map[2 * c + 1] * BK_CHUNK;
+    const long long left = sg.n - start;
+    const int cnt = left < BK_CHUNK ? (int)left : BK_CHUNK;
+    gfloat* p = (gfloat*)sg.p + start;                        // (pointers read from the table: say that they are global memory)
+    gfloat* sh = EM ? (gfloat*)sg.shadow + start : nullptr;
+    const float* g = AD ? gflat + sg.offset + start : nullptr;
+    float* m = AD ? mflat + sg.offset + start : nullptr;
+    float* v = AD ? vflat + sg.offset + start : nullptr;
+    const bool vec = (((uintptr_t)p | (EM ? (uintptr_t)sh : 0)) & 15) == 0;
+    int done = 0;
+    if (vec) {
+      done = cnt & ~3;
+#pragma unroll
+      for (int j = 0; j < BK_CHUNK / 1024; ++j) {
+        const int i = j * 1024 + threadIdx.x * 4;
+        if (i + 3 < cnt) {
+          f32x4 pv = *(const gf32x4*)(p + i);
+          f32x4 sv = {0.f, 0.f, 0.f, 0.f}, gv = sv, mv = sv, vv = sv;
+          if (EM) sv = *(const gf32x4*)(sh + i);
+          if (AD) {
+            gv = *reinterpret_cast<const f32x4*>(g + i);
+            mv = *reinterpret_cast<const f32x4*>(m + i);
+            vv = *reinterpret_cast<const f32x4*>(v + i);
+          }
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float pe = pv[e], se = sv[e], me = mv[e], ve = vv[e];
+            bucket_element<MODE>(pe, se, gv[e], me, ve, k, omd);
+            pv[e] = pe; sv[e] = se; mv[e] = me; vv[e] = ve;
+          }
+          if (AD) {
+            *reinterpret_cast<f32x4*>(m + i) = mv;
+            *reinterpret_cast<f32x4*>(v + i) = vv;
+            *(gf32x4*)(p + i) = pv;
+          }
+          if (EM) *(gf32x4*)(sh + i) = sv;
+        }
+      }
+    }
+    for (int i = done + threadIdx.x; i < cnt; i += 256) {       // the segment's ragged end; every element of an unaligned segment
+      float pi = p[i], si = EM ? sh[i] : 0.f, mi = AD ? m[i] : 0.f, vi = AD ? v[i] : 0.f;
+      bucket_element<MODE>(pi, si, AD ? g[i] : 0.f, mi, vi, k, omd);
+      if (AD) { m[i] = mi; v[i] = vi; p[i] = pi; }
+      if (EM) sh[i] = si;
+    }
+  }
+}
+
+// p <-> shadow over the same table (LitEma.store + copy_to, and restore: its own inverse)
+__global__ void __launch_bounds__(256) bucket_swap_kernel(const BucketSegment* __restrict__ segs, const int* __restrict__ chunk_map,
+                                                          int n_chunks) {
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const BucketSegment sg = segs[chunk_map[2 * c]];
+    const long long start = (long long)chunk_map[2 * c + 1] * BK_CHUNK;
+    const long long left = sg.n - start;
+    const int cnt = left < BK_CHUNK ? (int)left : BK_CHUNK;
+    gfloat* p = (gfloat*)sg.p + start;
+    gfloat* sh = (gfloat*)sg.shadow + start;
+    int done = 0;
+    if ((((uintptr_t)p | (uintptr_t)sh) & 15) == 0) {
+      done = cnt & ~3;
+#pragma unroll
+      for (int j = 0; j < BK_CHUNK / 1024; ++j) {
+        const int i = j * 1024 + threadIdx.x * 4;
+        if (i + 3 < cnt) {
+          const f32x4 pv = *(const gf32x4*)(p + i);
+          const f32x4 sv = *(const gf32x4*)(sh + i);
+          *(gf32x4*)(p + i) = sv;
+          *(gf32x4*)(sh + i) = pv;
+        }
+      }
+    }
+    for (int i = done + threadIdx.x; i < cnt; i += 256) {
+      const float pi = p[i], si = sh[i];
+      p[i] = si;
+      sh[i] = pi;
+    }
+  }
 }
 
 }  // namespace
@@ -1645,7 +1775,7 @@ extern "C" int32_t udt_colparts(int64_t rows) {
   return (int32_t)(wgs * 4);
 }
 
-extern "C" int udt_colsum_bf16(const void* x, float* partials, float* out, int64_t rows, int32_t C, void* stream) {
+static int colsum_impl(const void* x, float* partials, float* out, int64_t rows, int32_t C, int32_t accumulate, void* stream) {
   if (!x || !partials || !out) return UDT_ERR_BAD_ARG;
   if (rows <= 0 || C <= 0 || C % 2 != 0) return UDT_ERR_BAD_SHAPE;
   UDT_BWD_STREAM;
@@ -1653,13 +1783,21 @@ extern "C" int udt_colsum_bf16(const void* x, float* partials, float* out, int64
   const int rpw = (int)((rows + wgs - 1) / wgs);
   hipLaunchKernelGGL(colsum_partial_kernel, dim3(wgs), dim3(256), 0, s, static_cast<const uint16_t*>(x), partials, (long long)rows, C, rpw);
   UDT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(reduce_rows_f32_kernel, dim3((C + 15) / 16), dim3(256), 0, s, partials, out, parts, (long long)C, 0);
+  hipLaunchKernelGGL(reduce_rows_f32_kernel, dim3((C + 15) / 16), dim3(256), 0, s, partials, out, parts, (long long)C, accumulate);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
 }
 
-extern "C" int udt_ln_param_grad(const void* x, const void* dy, float* partials, float* dgamma_dbeta, int64_t rows, int32_t C, float eps,
-                                 void* stream) {
+extern "C" int udt_colsum_bf16(const void* x, float* partials, float* out, int64_t rows, int32_t C, void* stream) {
+  return colsum_impl(x, partials, out, rows, C, 0, stream);
+}
+
+extern "C" int udt_colsum_bf16_acc(const void* x, float* partials, float* out, int64_t rows, int32_t C, int32_t accumulate, void* stream) {
+  return colsum_impl(x, partials, out, rows, C, accumulate, stream);
+}
+
+static int ln_param_grad_impl(const void* x, const void* dy, float* partials, float* dgamma_dbeta, int64_t rows, int32_t C, float eps,
+                              int32_t accumulate, void* stream) {
   if (!x || !dy || !partials || !dgamma_dbeta) return UDT_ERR_BAD_ARG;
   if (rows <= 0 || C <= 0 || C % 8 != 0 || C > 2048) return UDT_ERR_BAD_SHAPE;
   UDT_BWD_STREAM;
@@ -1676,9 +1814,20 @@ extern "C" int udt_ln_param_grad(const void* x, const void* dy, float* partials,
     default: return UDT_ERR_BAD_SHAPE;
   }
   UDT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(reduce_rows_f32_kernel, dim3((2 * C + 15) / 16), dim3(256), 0, s, partials, dgamma_dbeta, parts, (long long)2 * C, 0);
+  hipLaunchKernelGGL(reduce_rows_f32_kernel, dim3((2 * C + 15) / 16), dim3(256), 0, s, partials, dgamma_dbeta, parts, (long long)2 * C,
+                     accumulate);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
+}
+
+extern "C" int udt_ln_param_grad(const void* x, const void* dy, float* partials, float* dgamma_dbeta, int64_t rows, int32_t C, float eps,
+                                 void* stream) {
+  return ln_param_grad_impl(x, dy, partials, dgamma_dbeta, rows, C, eps, 0, stream);
+}
+
+extern "C" int udt_ln_param_grad_acc(const void* x, const void* dy, float* partials, float* dgamma_dbeta, int64_t rows, int32_t C, float eps,
+                                     int32_t accumulate, void* stream) {
+  return ln_param_grad_impl(x, dy, partials, dgamma_dbeta, rows, C, eps, accumulate, stream);
 }
 
 extern "C" int32_t udt_wgrad_splits(int64_t R, int32_t N, int32_t K) {
@@ -1691,8 +1840,8 @@ extern "C" int32_t udt_wgrad_splits(int64_t R, int32_t N, int32_t K) {
   return (int32_t)S;
 }
 
-extern "C" int udt_wgrad_bf16(const void* dy, const void* x, float* dw, float* partials, int64_t R, int32_t N, int32_t K, int32_t ldy,
-                              int32_t ldx, void* stream) {
+static int wgrad_impl(const void* dy, const void* x, float* dw, float* partials, int64_t R, int32_t N, int32_t K, int32_t ldy, int32_t ldx,
+                      int32_t accumulate, void* stream) {
   if (!dy || !x || !dw) return UDT_ERR_BAD_ARG;
   if (R <= 0 || R > 0x7fffff00LL || N <= 0 || K <= 0 || N % 8 != 0 || K % 8 != 0 || ldy < N || ldx < K || ldy % 8 != 0 || ldx % 8 != 0)
     return UDT_ERR_BAD_SHAPE;
@@ -1705,14 +1854,24 @@ extern "C" int udt_wgrad_bf16(const void* dy, const void* x, float* dw, float* p
   const int S_used = (int)((R + rps - 1) / rps);                // (rounding the range up to whole steps may need fewer of them)
   float* dst = S_used > 1 ? partials : dw;
   hipLaunchKernelGGL(wgrad_kernel, dim3((K + 127) / 128, (N + 127) / 128, S_used), dim3(256), 0, s, static_cast<const uint16_t*>(dy),
-                     static_cast<const uint16_t*>(x), dst, (int)R, N, K, ldy, ldx, rps);
+                     static_cast<const uint16_t*>(x), dst, (int)R, N, K, ldy, ldx, rps, S_used > 1 ? 0 : accumulate);
   UDT_CHECK_LAUNCH();
   if (S_used > 1) {
     const long long n = (long long)N * K;
-    hipLaunchKernelGGL(reduce_rows_f32_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, partials, dw, S_used, n, 0);
+    hipLaunchKernelGGL(reduce_rows_f32_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, partials, dw, S_used, n, accumulate);
     UDT_CHECK_LAUNCH();
   }
   return UDT_OK;
+}
+
+extern "C" int udt_wgrad_bf16(const void* dy, const void* x, float* dw, float* partials, int64_t R, int32_t N, int32_t K, int32_t ldy,
+                              int32_t ldx, void* stream) {
+  return wgrad_impl(dy, x, dw, partials, R, N, K, ldy, ldx, 0, stream);
+}
+
+extern "C" int udt_wgrad_bf16_acc(const void* dy, const void* x, float* dw, float* partials, int64_t R, int32_t N, int32_t K, int32_t ldy,
+                                  int32_t ldx, int32_t accumulate, void* stream) {
+  return wgrad_impl(dy, x, dw, partials, R, N, K, ldy, ldx, accumulate, stream);
 }
 
 extern "C" int32_t udt_xattn_kv_splits(int32_t nq) { return nq <= 0 ? 0 : (nq + XKV_QT - 1) / XKV_QT; }
@@ -1794,6 +1953,47 @@ extern "C" int udt_adamw_f32(float* p, const float* g, float* m, float* v, int64
   const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, (long long)n, lr, beta1, beta2, eps,
                      weight_decay, bc1, sqrtf(bc2), grad_scale);
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}
+
+static_assert(sizeof(udt_bucket_segment) == sizeof(BucketSegment) && sizeof(BucketSegment) == 32, "segment table layout");
+
+static unsigned bucket_grid(int32_t n_chunks) { return (unsigned)(n_chunks < 2048 ? n_chunks : 2048); }   // 8 workgroups per CU, grid-strided
+
+extern "C" int udt_bucket_update_f32(const udt_bucket_segment* segments, const int32_t* chunk_map, int32_t n_chunks, float* g, float* m,
+                                     float* v, int32_t mode, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                     int32_t step, float grad_scale, float one_minus_decay, void* stream) {
+  if (!segments || !chunk_map) return UDT_ERR_BAD_ARG;
+  if (mode < 1 || mode > 3 || n_chunks <= 0) return UDT_ERR_BAD_SHAPE;
+  if (mode & 1) {
+    if (!g || !m || !v) return UDT_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) return UDT_ERR_BAD_ARG;
+    if (step <= 0) return UDT_ERR_BAD_SHAPE;
+  }
+  UDT_BWD_STREAM;
+  AdamwCoefs k = {lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale};
+  if (mode & 1) {
+    k.bc1 = 1.0f - powf(beta1, (float)step);
+    k.bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
+  }
+  const BucketSegment* sg = reinterpret_cast<const BucketSegment*>(segments);
+  const dim3 grid(bucket_grid(n_chunks));
+  switch (mode) {
+    case 1: hipLaunchKernelGGL(bucket_update_kernel<1>, grid, dim3(256), 0, s, sg, chunk_map, n_chunks, g, m, v, k, one_minus_decay); break;
+    case 2: hipLaunchKernelGGL(bucket_update_kernel<2>, grid, dim3(256), 0, s, sg, chunk_map, n_chunks, g, m, v, k, one_minus_decay); break;
+    default: hipLaunchKernelGGL(bucket_update_kernel<3>, grid, dim3(256), 0, s, sg, chunk_map, n_chunks, g, m, v, k, one_minus_decay); break;
+  }
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}
+
+extern "C" int udt_bucket_swap_f32(const udt_bucket_segment* segments, const int32_t* chunk_map, int32_t n_chunks, void* stream) {
+  if (!segments || !chunk_map) return UDT_ERR_BAD_ARG;
+  if (n_chunks <= 0) return UDT_ERR_BAD_SHAPE;
+  UDT_BWD_STREAM;
+  hipLaunchKernelGGL(bucket_swap_kernel, dim3(bucket_grid(n_chunks)), dim3(256), 0, s, reinterpret_cast<const BucketSegment*>(segments),
+                     chunk_map, n_chunks);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
 }

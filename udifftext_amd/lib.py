@@ -50,6 +50,14 @@ class SamplerCoefs(C.Structure):
                 ("c_out", C.c_float), ("scale", C.c_float)]
 
 
+class BucketSegment(C.Structure):
+    """udt_bucket_segment: one trained tensor of the fused optimiser step"""
+    _fields_ = [("p", C.c_void_p), ("shadow", C.c_void_p), ("offset", C.c_int64), ("n", C.c_int64)]
+
+
+BUCKET_CHUNK = 4096                                  # UDT_BUCKET_CHUNK
+BUCKET_ADAMW, BUCKET_EMA = 1, 2
+
 MULTISTEP_MAX = 8                                    # UDT_MULTISTEP_MAX
 
 
@@ -159,6 +167,11 @@ SYMBOLS = {
     "udt_diff_loss_grad": (C.c_int, [_fp, _fp, _fp, _fp, _vp, _fp, _i32, _i32, _i32, _i32, _vp]),
     "udt_precond_loss_grad": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _i32, _i32, _i32, _i32, _vp]),
     "udt_adamw_f32": (C.c_int, [_fp, _fp, _fp, _fp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp]),
+    "udt_wgrad_bf16_acc": (C.c_int, [_vp, _vp, _fp, _fp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "udt_colsum_bf16_acc": (C.c_int, [_vp, _fp, _fp, _i64, _i32, _i32, _vp]),
+    "udt_ln_param_grad_acc": (C.c_int, [_vp, _vp, _fp, _fp, _i64, _i32, _f32, _i32, _vp]),
+    "udt_bucket_update_f32": (C.c_int, [_vp, _vp, _i32, _fp, _fp, _fp, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _vp]),
+    "udt_bucket_swap_f32": (C.c_int, [_vp, _vp, _i32, _vp]),
     "udt_add_bf16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "udt_debug_set": (C.c_int, [C.c_char_p, _i32]),
     "udt_bias_add_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),

@@ -1160,43 +1160,67 @@ def transpose(x: torch.Tensor) -> torch.Tensor:
 WGRAD_KERNEL = os.environ.get("UDT_WGRAD_KERNEL", "1") != "0"     # 0: transposes + the forward GEMM (A/B, tests)
 
 
-def weight_grad(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+def _acc_dst(out: torch.Tensor, shape) -> None:
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(shape), (out.dtype, out.shape, shape)
+
+
+def weight_grad(dy: torch.Tensor, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dW fp32 [N, K] = dy^T x for dy bf16 [M, N], x bf16 [M, K] (nn.Linear: y = x W^T), contraction over the M rows with fp32
     accumulation and output: udt_wgrad_bf16 straight from the row-major operands (or, switched off / for shapes it does not take, the
-    forward GEMM on the two operands transposed)"""
+    forward GEMM on the two operands transposed).  ``out``: an fp32 [N, K] view (a gradient bucket's) that the result is ADDED to —
+    udt_wgrad_bf16_acc; the fallback adds its result with udt_axpy_f32"""
     _bf16(dy); _bf16(x)
     assert dy.dim() == 2 and x.dim() == 2 and dy.shape[0] == x.shape[0] and dy.stride(1) == 1 and x.stride(1) == 1
     R, N = dy.shape
     K = x.shape[1]
     lib = L.load()
+    if out is not None:
+        _acc_dst(out, (N, K))
     if not WGRAD_KERNEL or N % 8 or K % 8 or dy.stride(0) % 8 or x.stride(0) % 8 or (dy.data_ptr() | x.data_ptr()) & 15:
-        return linear(transpose(dy), transpose(x), None, flags=L.GEMM_OUT_F32)
-    dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
+        dw = linear(transpose(dy), transpose(x), None, flags=L.GEMM_OUT_F32)
+        if out is None:
+            return dw
+        axpy_(out.view(-1), dw.contiguous().view(-1), 1.0)
+        return out
     S = lib.udt_wgrad_splits(R, N, K)
     part = torch.empty((S, N, K), dtype=torch.float32, device=dy.device) if S > 1 else None
+    if out is not None:
+        L.check(lib.udt_wgrad_bf16_acc(_ptr(dy), _ptr(x), _ptr(out), _ptr(part), R, N, K, dy.stride(0), x.stride(0), 1, _stream()),
+                "udt_wgrad_bf16_acc")
+        return out
+    dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
     L.check(lib.udt_wgrad_bf16(_ptr(dy), _ptr(x), _ptr(dw), _ptr(part), R, N, K, dy.stride(0), x.stride(0), _stream()), "udt_wgrad_bf16")
     return dw
 
 
-def colsum(x: torch.Tensor) -> torch.Tensor:
-    """fp32 [C] column sums of bf16 [rows, C] (bias gradient)"""
+def colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [C] column sums of bf16 [rows, C] (bias gradient); ``out``: an fp32 [C] view the sums are ADDED to (udt_colsum_bf16_acc)"""
     _bf16(x)
     assert x.is_contiguous() and x.dim() == 2
     rows, Cc = x.shape
     lib = L.load()
     part = torch.empty((lib.udt_colparts(rows), Cc), dtype=torch.float32, device=x.device)
+    if out is not None:
+        _acc_dst(out, (Cc,))
+        L.check(lib.udt_colsum_bf16_acc(_ptr(x), _ptr(part), _ptr(out), rows, Cc, 1, _stream()), "udt_colsum_bf16_acc")
+        return out
     out = torch.empty((Cc,), dtype=torch.float32, device=x.device)
     L.check(lib.udt_colsum_bf16(_ptr(x), _ptr(part), _ptr(out), rows, Cc, _stream()), "udt_colsum_bf16")
     return out
 
 
-def layer_norm_param_grad(x: torch.Tensor, dy: torch.Tensor, eps: float = 1e-5):
-    """(d gamma, d beta) fp32 [C] each of LayerNorm over bf16 rows x with output cotangent dy"""
+def layer_norm_param_grad(x: torch.Tensor, dy: torch.Tensor, eps: float = 1e-5, out: Optional[torch.Tensor] = None):
+    """(d gamma, d beta) fp32 [C] each of LayerNorm over bf16 rows x with output cotangent dy; ``out``: an fp32 [2, C] view
+    (d gamma over d beta) both are ADDED to (udt_ln_param_grad_acc)"""
     _bf16(x); _bf16(dy)
     assert x.is_contiguous() and dy.is_contiguous() and x.shape == dy.shape and x.dim() == 2
     rows, Cc = x.shape
     lib = L.load()
     part = torch.empty((lib.udt_colparts(rows), 2, Cc), dtype=torch.float32, device=x.device)
+    if out is not None:
+        _acc_dst(out, (2, Cc))
+        L.check(lib.udt_ln_param_grad_acc(_ptr(x), _ptr(dy), _ptr(part), _ptr(out), rows, Cc, eps, 1, _stream()), "udt_ln_param_grad_acc")
+        return out[0], out[1]
     out = torch.empty((2, Cc), dtype=torch.float32, device=x.device)
     L.check(lib.udt_ln_param_grad(_ptr(x), _ptr(dy), _ptr(part), _ptr(out), rows, Cc, eps, _stream()), "udt_ln_param_grad")
     return out[0], out[1]
@@ -1280,6 +1304,28 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, s
     L.check(L.load().udt_adamw_f32(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay, step,
                                    grad_scale, _stream()), "udt_adamw_f32")
     torch._C._increment_version(p)
+
+
+def bucket_update_(segments: torch.Tensor, chunk_map: torch.Tensor, g: Optional[torch.Tensor], m: Optional[torch.Tensor],
+                   v: Optional[torch.Tensor], mode: int, *, step: int = 0, lr: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
+                   weight_decay: float = 0.0, grad_scale: float = 1.0, one_minus_decay: float = 0.0) -> None:
+    """the fused optimiser step over a device table of segments (udt_bucket_update_f32): ``segments`` uint8 [n_seg * 32] (an array of
+    lib.BucketSegment), ``chunk_map`` int32 [n_chunks, 2]; mode = lib.BUCKET_ADAMW | lib.BUCKET_EMA.  The caller bumps the versions
+    of the tensors behind the table's pointers"""
+    assert chunk_map.dtype == torch.int32 and chunk_map.is_contiguous() and chunk_map.dim() == 2 and chunk_map.shape[1] == 2
+    assert segments.dtype == torch.uint8 and segments.is_contiguous() and segments.numel() % C.sizeof(L.BucketSegment) == 0
+    for t in (g, m, v):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    L.check(L.load().udt_bucket_update_f32(_ptr(segments), _ptr(chunk_map), chunk_map.shape[0], _ptr(g), _ptr(m), _ptr(v), mode, lr,
+                                           betas[0], betas[1], eps, weight_decay, step, grad_scale, one_minus_decay, _stream()),
+            "udt_bucket_update_f32")
+
+
+def bucket_swap_(segments: torch.Tensor, chunk_map: torch.Tensor) -> None:
+    """p <-> shadow over a device table of segments (udt_bucket_swap_f32)"""
+    assert chunk_map.dtype == torch.int32 and chunk_map.is_contiguous() and chunk_map.dim() == 2 and chunk_map.shape[1] == 2
+    assert segments.dtype == torch.uint8 and segments.is_contiguous()
+    L.check(L.load().udt_bucket_swap_f32(_ptr(segments), _ptr(chunk_map), chunk_map.shape[0], _stream()), "udt_bucket_swap_f32")
 
 
 # ------------------------------------------------------------------------------------------ profiling

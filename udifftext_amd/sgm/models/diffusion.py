@@ -2,10 +2,16 @@
 sampler reaches into (``model.denoiser``, ``model.model``, ``model.conditioner``, ``model.first_stage_model``,
 ``model.loss_fn``) — reference sgm/models/diffusion.py:22-136.  A plain ``nn.Module`` (no Lightning).  Round 6: the training half's
 core — ``forward`` (the loss), ``shared_step`` / ``training_step`` and ``configure_optimizers`` (:138-172,202-222) — runs on the
-HIP path's written-out reverse pass (udifftext_amd.training); EMA, logging and log_images stay out of scope.
+HIP path's written-out reverse pass (udifftext_amd.training); logging and log_images stay out of scope.
+
+``use_ema`` keeps ``model_ema`` (:75-78; udifftext_amd.training.Ema: LitEma's buffers for the tensors opt_keys trains),
+``on_train_batch_end`` moves it (:178-180) and ``ema_scope`` runs a block on the EMA weights (:182-195).
+``configure_optimizers(fused=True, accumulate_grad_batches=N)`` returns the fused bucket optimiser; ``training_step`` with it is one
+micro-batch of a window of N (configs/train.yaml:21): the optimiser steps on the N-th, the EMA moves after every one.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from typing import List, Union
 
 import torch
@@ -25,8 +31,6 @@ class DiffusionEngine(nn.Module):
                  log_keys: Union[List, None] = None, no_cond_log: bool = False, compile_model: bool = False,
                  opt_keys: Union[List, None] = None):
         super().__init__()
-        if use_ema:
-            raise NotImplementedError("EMA weights are a training feature (out of scope)")
         self.opt_keys, self.log_keys, self.input_key = opt_keys, log_keys, input_key
         self.optimizer_config = default(optimizer_config, {"target": "torch.optim.AdamW"})
         network = instantiate_from_config(network_config)
@@ -37,7 +41,11 @@ class DiffusionEngine(nn.Module):
         self.scheduler_config = scheduler_config
         self._init_first_stage(first_stage_config)
         self.loss_fn = instantiate_from_config(loss_fn_config) if loss_fn_config is not None else None
-        self.use_ema = False
+        self.use_ema = bool(use_ema)
+        self.ema_decay_rate = ema_decay_rate
+        self.model_ema = None
+        if self.use_ema:
+            self._build_ema()
         self.scale_factor = scale_factor
         self.disable_first_stage_autocast = disable_first_stage_autocast
         self.no_cond_log = no_cond_log
@@ -119,29 +127,80 @@ class DiffusionEngine(nn.Module):
         loss_dict, _ = training.training_loss_and_grads(self, x, cond, batch["seg"], batch["seg_mask"], want_grads=False)
         return loss_dict["loss/full_loss"], loss_dict
 
-    def shared_step(self, batch):
-        """reference :144-149 (latents from the first stage, then the loss) — with the gradients of the trained parameters"""
+    def shared_step(self, batch, bucket=None):
+        """reference :144-149 (latents from the first stage, then the loss) — with the gradients of the trained parameters (added
+        to ``bucket``, a training.GradBucket, when one is given)"""
         from udifftext_amd import training
         x = self.encode_first_stage(self.get_input(batch))
         cond = self.conditioner(batch)
-        return training.training_loss_and_grads(self, x, cond, batch["seg"], batch["seg_mask"])
+        return training.training_loss_and_grads(self, x, cond, batch["seg"], batch["seg_mask"], bucket=bucket)
 
-    def configure_optimizers(self, learning_rate: float = 5.0e-5):
+    def _build_ema(self) -> None:
+        """reference :75-78, for the tensors opt_keys trains (LitEma moves no others, sgm/modules/ema.py:46-54); without opt_keys
+        there is nothing to shadow yet: ``configure_optimizers(fused=True)`` builds it then"""
+        from udifftext_amd import training
+        named = training.trainable_parameters(self)
+        if named:
+            trained = {n for n, _ in named}
+            rest = [n for n in ("model." + k for k, _ in self.model.named_parameters()) if n not in trained]
+            self.model_ema = training.Ema(named, decay=self.ema_decay_rate, untrained_names=rest)
+
+    def configure_optimizers(self, learning_rate: float = 5.0e-5, fused: bool = False, accumulate_grad_batches: int = 1):
         """reference :202-222: AdamW (the default optimizer_config) over the parameters whose names contain an ``opt_keys`` entry;
-        the LambdaLR 0.95^epoch is ``optimizer.set_epoch``"""
+        the LambdaLR 0.95^epoch is ``optimizer.set_epoch``.  ``fused``: the bucket optimiser (training.BucketAdamW: one gradient
+        bucket, one update launch, windows of ``accumulate_grad_batches`` micro-batches — configs/train.yaml:21); with ``use_ema``
+        it also makes sure ``model_ema`` exists"""
         from udifftext_amd import training
         if self.optimizer_config.get("target", "torch.optim.AdamW") != "torch.optim.AdamW":
             raise NotImplementedError("udt_adamw_f32 implements the reference's default optimiser (torch.optim.AdamW)")
         named = training.trainable_parameters(self)
         if not named:
             raise ValueError("opt_keys selects no parameter (configs/train/textdesign_sd_2.yaml: t_attn, t_norm)")
-        return training.AdamW(named, lr=learning_rate, **self.optimizer_config.get("params", {}))
+        if not fused:
+            if accumulate_grad_batches != 1:
+                raise NotImplementedError("gradient accumulation runs on the fused optimiser: configure_optimizers(fused=True)")
+            return training.AdamW(named, lr=learning_rate, **self.optimizer_config.get("params", {}))
+        if self.use_ema and (self.model_ema is None or self.model_ema.names != [n for n, _ in named]):
+            self._build_ema()
+        return training.BucketAdamW(named, lr=learning_rate, accumulate_grad_batches=accumulate_grad_batches,
+                                    **self.optimizer_config.get("params", {}))
+
+    def on_train_batch_end(self, *args, **kwargs):
+        """reference :178-180: the EMA update, after every micro-batch.  ``training_step`` already does it, on either optimiser (it
+        is Lightning's whole per-batch sequence): this hook is for a caller that drives ``shared_step`` and the optimiser itself;
+        calling it after ``training_step`` would count the update twice"""
+        if self.use_ema and self.model_ema is not None:
+            self.model_ema.update()
+
+    @contextmanager
+    def ema_scope(self, context=None):
+        """reference :182-195: the block runs on the EMA weights (parameters and shadows trade places, udt_bucket_swap_f32, and trade
+        back); a no-op without use_ema"""
+        on = self.use_ema and self.model_ema is not None
+        if on:
+            self.model_ema.store()
+            self.model_ema.copy_to()
+            if context is not None:
+                print(f"{context}: Switched to EMA weights")
+        try:
+            yield None
+        finally:
+            if on:
+                self.model_ema.restore()
+                if context is not None:
+                    print(f"{context}: Restored training weights")
 
     def training_step(self, batch, optimizer, dist=None):
         """reference :151-172 + the optimiser step Lightning takes after it: loss, gradients, rank average (``dist``), AdamW update;
-        returns the loss dict"""
+        returns the loss dict.  With the fused optimiser: one micro-batch of its window (training.window_step) — backward into the
+        bucket, on the N-th call the update, after every call on_train_batch_end (the EMA), fused into the update's launch.  Either way
+        the EMA update is part of this call: do not call ``on_train_batch_end`` after it"""
         from udifftext_amd import training
+        if isinstance(optimizer, training.BucketAdamW):
+            return training.window_step(optimizer, lambda bucket: self.shared_step(batch, bucket=bucket)[0], dist,
+                                        ema=training.engine_ema(self))
         loss_dict, grads = self.shared_step(batch)
         training.allreduce_gradients(grads, [n for n, _ in optimizer.named], dist)
         optimizer.step(grads)
+        self.on_train_batch_end()                                       # (the per-tensor route: the EMA-only launch, when use_ema)
         return loss_dict
