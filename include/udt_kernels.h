@@ -55,6 +55,7 @@
  *                                                         (configs/train.yaml:21 accumulate_grad_batches)
  *     udt_bucket_update_f32, udt_bucket_swap_f32          AdamW.step over every trained tensor + LitEma.forward (sgm/modules/ema.py:33-52),
  *                                                         LitEma.store / copy_to / restore (ema.py:56-86), one launch each
+ *     udt_aae_row_update_f32                              the attend-and-excite update and exit rule (sampling.py:247-250), row by row
  *     (backward-data of linears and convolutions: udt_gemm on re-packed weights)
  *
  * Conventions
@@ -639,6 +640,19 @@ int udt_bucket_update_f32(const udt_bucket_segment* segments, const int32_t* chu
 int udt_bucket_swap_f32(const udt_bucket_segment* segments, const int32_t* chunk_map, int32_t n_chunks, void* stream);
 /* x fp32 += a * y fp32: the attend-and-excite update x <- x - alpha * grad (sampling.py:247) */
 int udt_axpy_f32(float* x, const float* y, float a, int64_t n, void* stream);
+/* The attend-and-excite update with every row of a batch on its own B = 1 loop (sampling.py:240-252), one launch per iteration.
+ * x, grad fp32 [B, n] contiguous; loss fp32 [B] (the loss of the evaluation that produced grad); state_in / state_out int32 [2, B]:
+ * row 0 the active flags, row 1 the per-row update counts, two DISTINCT buffers the caller swaps between iterations; n_active: one int32.
+ * For row b with a = (state_in[b] != 0):
+ *   a:      x[b, :] <- fma(-alpha, grad[b, :], x[b, :])   (bit-identical to udt_axpy_f32(x_b, grad_b, -alpha, n))
+ *   not a:  x[b, :] is not written, and nothing written anywhere depends on grad[b, :] or loss[b]
+ *   it = state_in[B + b] + a;  state_out[B + b] = it
+ *   state_out[b] = a && iter_enabled && !(loss[b] <= thres) && !(it > max_iter)      (:249; a NaN loss runs to the cap)
+ *   *n_active = sum_b state_out[b]
+ * UDT_ERR_BAD_ARG: a null pointer, B < 1, n < 1, max_iter < 0, state_in and state_out overlapping; UDT_ERR_BAD_SHAPE: n % 4 != 0,
+ * x / grad not 16-byte aligned, B > 1024.  Nothing is launched in either case. */
+int udt_aae_row_update_f32(float* x, const float* grad, const float* loss, const int32_t* state_in, int32_t* state_out, int32_t* n_active,
+                           int32_t B, int64_t n, float alpha, float thres, int32_t iter_enabled, int32_t max_iter, void* stream);
 /* x bf16 += y bf16 (n elements, n % 8 == 0) ; utility for residuals outside GEMM epilogues */
 int udt_add_bf16(void* x, const void* y, int64_t n, void* stream);
 

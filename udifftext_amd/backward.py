@@ -490,5 +490,24 @@ class GraphedLocalLossGrad:
         self.graph.replay()
         return self.loss, self.grad
 
+    # the row-wise attend-and-excite loop (EulerEDMSampler.attend_and_excite_rows) keeps its latent IN the static buffer: the inputs
+    # are copied once per update step, every iteration is one replay and one in-place update of ``x``
+    @property
+    def x(self) -> torch.Tensor:
+        """the static latent the graph reads (fp32, the shape it was built for)"""
+        return self.inputs[0]
+
+    def load(self, x, timesteps, concat, t_context, mask, seg_mask) -> None:
+        """copy the six inputs into the static buffers (capturing on first use) without running the graph"""
+        for dst, src in zip(self.inputs, (x, timesteps, concat, t_context, mask, seg_mask)):
+            dst.copy_(src)
+        if self.graph is None:
+            self._capture()
+
+    def replay(self):
+        """run the graph on the static buffers as they are -> the static (loss, grad), valid until the next replay"""
+        self.graph.replay()
+        return self.loss, self.grad
+
     def check(self) -> None:
         self.ws.check()

@@ -918,6 +918,49 @@ __global__ void __launch_bounds__(256) axpy_f32_kernel(float* __restrict__ x, co
   if (i < n) x[i] = __builtin_fmaf(a, y[i], x[i]);
 }
 
+// The row-wise attend-and-excite update: every row b of a batch runs the reference's B = 1 loop (sampling.py:240-252) on its own.  state
+// int32 [2, B] = (active flags, update counts), read from state_in and written to state_out (distinct buffers: no workgroup depends on
+// another's write).  An active row takes x[b] <- fma(-alpha, grad[b], x[b]) (the arithmetic of axpy_f32_kernel), a frozen row is neither
+// read nor written, and neither its grad nor its loss is looked at.  grid (16-byte chunks of a row / 256, B); workgroup (0, 0) also
+// re-evaluates the exit rule for all B rows from state_in and loss, writes state_out and their sum n_active.
+__global__ void __launch_bounds__(256) aae_row_update_kernel(float* __restrict__ x, const float* __restrict__ grad,
+                                                             const float* __restrict__ loss, const int* __restrict__ state_in,
+                                                             int* __restrict__ state_out, int* __restrict__ n_active, int B, long long n4,
+                                                             float alpha, float thres, int iter_enabled, int max_iter) {
+  const int b = blockIdx.y;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (state_in[b] != 0 && i < n4) {
+    const float na = -alpha;
+    float4* xp = reinterpret_cast<float4*>(x) + (long long)b * n4 + i;
+    const float4 g = reinterpret_cast<const float4*>(grad)[(long long)b * n4 + i];
+    float4 v = *xp;
+    v.x = __builtin_fmaf(na, g.x, v.x);
+    v.y = __builtin_fmaf(na, g.y, v.y);
+    v.z = __builtin_fmaf(na, g.z, v.z);
+    v.w = __builtin_fmaf(na, g.w, v.w);
+    *xp = v;
+  }
+  if (blockIdx.x != 0 || blockIdx.y != 0) return;
+  __shared__ int cnt[256];
+  int mine = 0;
+  for (int r = threadIdx.x; r < B; r += 256) {
+    const int a = state_in[r] != 0;
+    const int it = state_in[B + r] + a;
+    int next = 0;
+    if (a && iter_enabled && !(it > max_iter)) next = !(loss[r] <= thres);      // (a NaN loss is not <= thres: the row runs to the cap)
+    state_out[r] = next;
+    state_out[B + r] = it;
+    mine += next;
+  }
+  cnt[threadIdx.x] = mine;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) cnt[threadIdx.x] += cnt[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *n_active = cnt[0];
+}
+
 // ================================================================================================ training step (second half)
 // The reference trains the text cross-attention only (configs/train/textdesign_sd_2.yaml:4-6 opt_keys t_attn, t_norm: 75.9 M of the
 // UNet's parameters): FullLoss.__call__ (loss.py:131-176) = weighted eps-prediction loss + lambda * get_local_loss (loss.py:237-286).
@@ -1735,6 +1778,23 @@ extern "C" int udt_axpy_f32(float* x, const float* y, float a, int64_t n, void* 
   if (n <= 0) return UDT_ERR_BAD_SHAPE;
   UDT_BWD_STREAM;
   hipLaunchKernelGGL(axpy_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, y, a, (long long)n);
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}
+
+extern "C" int udt_aae_row_update_f32(float* x, const float* grad, const float* loss, const int32_t* state_in, int32_t* state_out,
+                                      int32_t* n_active, int32_t B, int64_t n, float alpha, float thres, int32_t iter_enabled,
+                                      int32_t max_iter, void* stream) {
+  if (!x || !grad || !loss || !state_in || !state_out || !n_active || B < 1 || n < 1 || max_iter < 0) return UDT_ERR_BAD_ARG;
+  if (n % 4 != 0 || B > 1024 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad)) & 15)) return UDT_ERR_BAD_SHAPE;
+  const uintptr_t si = reinterpret_cast<uintptr_t>(state_in), so = reinterpret_cast<uintptr_t>(state_out);
+  const uintptr_t sbytes = (uintptr_t)2 * (uintptr_t)B * sizeof(int32_t);
+  if (si < so + sbytes && so < si + sbytes) return UDT_ERR_BAD_ARG;              // ping-pong buffers: they must not overlap
+  const long long n4 = n / 4, gx = (n4 + 255) / 256;
+  if (gx > 0x7fffffffLL) return UDT_ERR_BAD_SHAPE;
+  UDT_BWD_STREAM;
+  hipLaunchKernelGGL(aae_row_update_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, s, x, grad, loss, state_in, state_out, n_active,
+                     B, n4, alpha, thres, iter_enabled, max_iter);
   UDT_CHECK_LAUNCH();
   return UDT_OK;
 }

@@ -1145,6 +1145,22 @@ def axpy_(x: torch.Tensor, y: torch.Tensor, a: float) -> torch.Tensor:
     return x
 
 
+def aae_row_update_(x: torch.Tensor, grad: torch.Tensor, loss: torch.Tensor, state_in: torch.Tensor, state_out: torch.Tensor,
+                    n_active: torch.Tensor, alpha: float, thres: float, iter_enabled: bool, max_iter: int) -> torch.Tensor:
+    """the row-wise attend-and-excite update (udt_aae_row_update_f32): active rows of x fp32 [B, ...] take x -= alpha * grad, in
+    place; state_in / state_out int32 [2, B] (active flags, update counts; two distinct buffers), n_active int32 [1]"""
+    assert x.dtype == torch.float32 == grad.dtype == loss.dtype and x.is_contiguous() and grad.is_contiguous() and loss.is_contiguous()
+    B = x.shape[0] if x.dim() else 0
+    assert x.shape == grad.shape and loss.numel() == B
+    for st in (state_in, state_out):
+        assert st.dtype == torch.int32 and st.is_contiguous() and tuple(st.shape) == (2, B)
+    assert n_active.dtype == torch.int32 and n_active.numel() == 1
+    L.check(L.load().udt_aae_row_update_f32(_ptr(x), _ptr(grad), _ptr(loss), _ptr(state_in), _ptr(state_out), _ptr(n_active), B,
+                                            x.numel() // max(B, 1), alpha, thres, int(bool(iter_enabled)), int(max_iter), _stream()),
+            "udt_aae_row_update_f32")
+    return x
+
+
 # ------------------------------------------------------------------------------------------ training step (csrc/backward.hip)
 def transpose(x: torch.Tensor) -> torch.Tensor:
     """bf16 [R, C] (row-strided view allowed) -> [C, Rp], Rp = R rounded up to 64, zero-padded (operand of a dW = dY^T X GEMM)"""

@@ -161,8 +161,51 @@ def _lane_streams(device: torch.device, n: int):
     return _LANE_STREAMS[key]
 
 
+def _predict_many_aae(cfgs, model, sampler, sample_rows, batches, units, device, image_seeds, record_losses):
+    """the attend-and-excite branch of ``predict_many``: sampling batch after sampling batch on the current stream (see there)"""
+    from udifftext_amd import ops
+    gpu = torch.device(device).type == "cuda"
+    draw_noise = getattr(sampler, "draw_step_noise", None)
+    out = []
+    for idx in units:
+        xs, cs, ucs, sizes, noises, masks, segs = [], [], [], [], [], [], []
+        with ops.launch_context(cu_share=1):
+            for gi in idx:
+                b, buc = prepare_batch(batches[gi], device)
+                seeds = image_seeds[gi] if image_seeds is not None else None
+                with (rng.per_image(seeds) if seeds is not None else contextlib.nullcontext()):
+                    c, uc = model.conditioner.get_unconditional_conditioning(
+                        b, batch_uc=buc, force_uc_zero_embeddings=cfgs.force_uc_zero_embeddings)
+                    xs.append(sampler.get_init_noise(cfgs, model, cond=c, batch=b, uc=uc))
+                    if draw_noise is not None:      # churned steps: the run's step noise, right after the initial noise
+                        noises.append(draw_noise(xs[-1].shape, xs[-1].device, None, cfgs.init_step))
+                cs.append(c)
+                ucs.append(uc)
+                sizes.append(xs[-1].shape[0])
+                masks.append(b["mask"])
+                segs.append(b["seg_mask"])
+            if any(x.shape[1:] != xs[0].shape[1:] for x in xs):
+                raise ValueError("batches fused into one sampling batch need one image size (use fuse=1)")
+            fx = torch.cat(xs, 0) if len(xs) > 1 else xs[0]
+            fc = _cat_cond(cs) if len(cs) > 1 else cs[0]
+            fuc = _cat_cond(ucs) if len(ucs) > 1 else ucs[0]
+            fb = {"mask": torch.cat(masks, 0) if len(masks) > 1 else masks[0], "seg_mask": torch.cat(segs, 0) if len(segs) > 1 else segs[0]}
+            kw = {}
+            if noises and noises[0] is not None:
+                kw["noise"] = torch.cat(noises, 1) if len(noises) > 1 else noises[0]      # [steps, fused batch, 4, h, w]
+            z = sample_rows(model, fx, fc, fb, fuc, init_step=cfgs.init_step, record_losses=record_losses, **kw)
+            img = torch.clamp((model.decode_first_stage(z) + 1.0) / 2.0, min=0.0, max=1.0)
+        o = 0
+        for nb in sizes:
+            out.append((img[o:o + nb], z[o:o + nb]))
+            o += nb
+    if gpu:
+        ops.check_async_errors()
+    return out
+
+
 def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] = None, in_flight: Optional[int] = None,
-                 fuse: Optional[int] = None, image_seeds: Optional[list] = None):
+                 fuse: Optional[int] = None, image_seeds: Optional[list] = None, record_losses: bool = True):
     """``predict`` over a list of batches in throughput mode: ``fuse`` consecutive batches are concatenated into one
     sampling batch, and up to ``in_flight`` such batches are processed concurrently, each on its own launch stream
     (a lane): conditioning (VAE encoder, label encoder), the sampling loop's hipGraph replays (EulerEDMSampler.sample_lane)
@@ -172,7 +215,13 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
     ``predict`` batch by batch would use; decoding runs on the fused batch.  With automatic fusing (``fuse`` 0) only consecutive
     batches of one image size are joined; an explicit ``fuse`` > 1 over batches of different sizes raises ValueError.
     ``image_seeds[k]`` (optional): one seed per image of batch k — its draws then come from per-image generators
-    (``rng.per_image``), independent of batching and sharding.  Returns [(samples, z), ...] in input order."""
+    (``rng.per_image``), independent of batching and sharding.  Returns [(samples, z), ...] in input order.
+    ``cfgs.aae_enabled`` (attend-and-excite; EulerEDMSampler): the sampling batches are formed in the same way, but run ONE AT A TIME
+    on the caller's stream, planned for the whole chip — no lanes, ``in_flight`` only enters the automatic fuse count: the update
+    loop reads one word back per iterated update, and a host blocked on that read cannot feed other lanes.  Every image runs its own
+    update loop inside the fused batch (EulerEDMSampler.attend_and_excite_rows), so its result still depends on its own inputs
+    alone.  ``record_losses`` goes to the sampler (per-row local losses of every step in ``sampler.last_row_losses``, of the last
+    sampling batch).  ``cfgs.detailed`` is refused."""
     from udifftext_amd import ops
     device = device or next(model.parameters()).device
     n = max(1, int(in_flight if in_flight is not None else IN_FLIGHT))
@@ -180,8 +229,12 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
     auto = f <= 0
     if auto:
         f = min(4, max(1, -(-len(batches) // n)))
-    if cfgs.aae_enabled or cfgs.detailed:
-        raise NotImplementedError("attend-and-excite / detailed dumps are out of scope (see EulerEDMSampler.__call__)")
+    if cfgs.detailed:
+        raise NotImplementedError("detailed dumps are out of scope (see EulerEDMSampler.__call__)")
+    aae_sampler = getattr(sampler, "sample_rows_with_attend_and_excite", None) if cfgs.aae_enabled else None
+    if cfgs.aae_enabled and aae_sampler is None:
+        raise NotImplementedError(f"attend-and-excite in predict_many needs a sampler with sample_rows_with_attend_and_excite "
+                                  f"(EulerEDMSampler), not {type(sampler).__name__}")
     # (host logic only below; with a stub engine on the CPU — tests/test_parallel_cpu.py — there are no streams)
     gpu = torch.device(device).type == "cuda"
     main = torch.cuda.current_stream(device) if gpu else None
@@ -209,6 +262,8 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
                 units.append([i])
     else:
         units = [list(range(i, min(i + f, len(batches)))) for i in range(0, len(batches), f)]
+    if aae_sampler is not None:
+        return _predict_many_aae(cfgs, model, sampler, aae_sampler, batches, units, device, image_seeds, record_losses)
     # lanes in use: as few as keep every lane equally loaded — 4 sampling batches on 3 lanes run as 2 + 2 on TWO lanes (each planned
     # for half of the CUs), not as 2 + 1 + 1 with the 4th batch alone on a lane planned for a third of the chip while two lanes idle
     rounds = -(-len(units) // n) if units else 1

@@ -918,6 +918,130 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         self.aae_evaluations = getattr(self, "aae_evaluations", 0) + iters     # (how many gradients a sampling run took)
         return x
 
+    # ------------------------------------------------------------------------- attend-and-excite, row by row
+    def _aae_rows_runner(self, model, unet, x, args):
+        """the captured evaluation ``attend_and_excite`` uses (one cache, one invalidation rule: shapes, weights, denoiser) with the
+        inputs loaded into its static buffers; None -> eager launches (graphs off, or capture unavailable)"""
+        from udifftext_amd import backward
+        if not (self.use_graphs and AAE_GRAPH):
+            return None
+        runner = getattr(self, "_aae_runner", None)
+        key = denoiser_key(model.denoiser)
+        if runner is None or not runner.valid_for(unet, x, *args) or getattr(self, "_aae_key", None) != key:
+            runner = self._aae_runner = None                               # (drop the old pool before the new capture)
+            try:
+                runner = backward.GraphedLocalLossGrad(unet, model.loss_fn, x, *args)
+                runner.load(x, *args)
+                self._aae_runner, self._aae_key = runner, key
+            except Exception as e:
+                if not _is_capture_failure(e):
+                    raise
+                print(f"[udifftext_amd] attend-and-excite: hipGraph capture unavailable ({type(e).__name__}: {e}); eager launches")
+                return None
+        else:
+            runner.load(x, *args)
+        return runner
+
+    def attend_and_excite_rows(self, x, model, sigma, cond, batch, alpha, iter_enabled, thres, max_iter=20):
+        """``attend_and_excite`` with every row of the batch on its OWN B = 1 loop (reference sampling.py:240-252 compares a
+        one-element loss): a row whose loss has fallen to ``thres``, or that has passed max_iter, is frozen — it takes no further
+        update, whatever its batch mates do — and the loop ends when no row is active.  A row's result therefore depends on its own
+        inputs alone (``attend_and_excite`` keeps updating every row while any is above thres).  Frozen rows are still evaluated:
+        the batch is not compacted.  One iteration is one graph replay on the runner's static latent, one udt_aae_row_update_f32
+        launch that updates it in place, and — only with iter_enabled — the read-back of one int32 (the number of active rows);
+        without iter_enabled there is exactly one evaluation and no host synchronisation.
+        -> (x, iters): iters int32 [B] on the device, the updates each row took.  At B = 1: ``attend_and_excite``, bit for bit."""
+        from udifftext_amd import backward
+        require_gpu(x, "EulerEDMSampler.attend_and_excite_rows")
+        c_noise = self.get_c_noise(x, model, sigma)
+        unet = model.model.diffusion_model
+        x = x.detach().clone().float().contiguous()
+        args = (c_noise.float(), cond["concat"], cond["t_crossattn"], batch["mask"], batch["seg_mask"])
+        B = x.shape[0]
+        runner = self._aae_rows_runner(model, unet, x, args)
+        if runner is not None:
+            xs, evaluate = runner.x, runner.replay
+        else:
+            xs, evaluate = x, lambda: backward.unet_local_loss_grad(unet, model.loss_fn, x, *args)
+        st = getattr(self, "_aae_rows_state", None)
+        if st is None or st[0].shape[1] != B or st[0].device != x.device:
+            st = self._aae_rows_state = (torch.empty((2, B), dtype=torch.int32, device=x.device),
+                                         torch.empty((2, B), dtype=torch.int32, device=x.device),
+                                         torch.empty((1,), dtype=torch.int32, device=x.device))
+        s_in, s_out, n_act = st
+        s_in[0].fill_(1)
+        s_in[1].zero_()
+        evals, frozen, active = 0, 0, B
+        while True:
+            loss, grad = evaluate()
+            ops.aae_row_update_(xs, grad, loss, s_in, s_out, n_act, float(alpha), float(thres), iter_enabled, max_iter)
+            s_in, s_out = s_out, s_in
+            evals += 1
+            frozen += B - active                                           # rows this evaluation computed for nothing
+            if not iter_enabled:
+                break
+            active = int(n_act.item())                                     # the iteration's one 4-byte read-back
+            if active == 0:
+                break
+        iters = s_in[1].clone()
+        if iter_enabled:
+            counts = iters.cpu().long()
+        else:
+            counts = torch.ones((B,), dtype=torch.long)                    # (known on the host: nothing is read back)
+        prev = getattr(self, "aae_row_updates", None)
+        self.aae_row_updates = counts if prev is None or prev.numel() != B else prev + counts
+        self.aae_evaluations = getattr(self, "aae_evaluations", 0) + evals
+        self.aae_frozen_row_evaluations = getattr(self, "aae_frozen_row_evaluations", 0) + frozen
+        return (xs.clone() if runner is not None else xs), iters
+
+    def sample_rows_with_attend_and_excite(self, model, x, cond, batch, uc, num_steps=None, init_step=0,
+                                           noise: Optional[torch.Tensor] = None, record_losses: bool = True):
+        """the attend-and-excite sampling loop for a batch of independent images (pipeline.predict_many): the schedule of
+        ``_sample_with_attend_and_excite`` — alpha = 20 sqrt(scale_i), iterated at steps 5, 9, ..., 25 down to thresholds
+        -0.5 ... -0.8, a churned step's noise added before the update, update and step at sigma_hat — with the update taken row by
+        row (``attend_and_excite_rows``), and without the per-step VAE decode, the GIF and the prints.  record_losses: every step
+        emits its attention maps and the per-row local loss goes into a device [steps, B] tensor, copied to ``last_row_losses``
+        once at the end; without it the steps are the fast steps (the latent then differs by the two text-attention forms'
+        rounding)."""
+        import numpy as np
+        self._check_fast_path(model)
+        require_gpu(x, "EulerEDMSampler.sample_rows_with_attend_and_excite")
+        uc = default(uc, cond)
+        if noise is None:
+            noise = self.draw_step_noise(x.shape, x.device, num_steps, init_step)
+        sig = self._host_sigmas(num_steps)
+        num_sigmas = len(sig)
+        x = x.float().contiguous()
+        x *= (1.0 + sig[0] ** 2.0) ** 0.5
+        scales = np.linspace(start=1.0, stop=0, num=num_sigmas)
+        iter_lst = np.linspace(start=5, stop=25, num=6, dtype=np.int32)
+        thres_lst = np.linspace(start=-0.5, stop=-0.8, num=6)
+        B = x.shape[0]
+        stepper = _Stepper(model, cond, uc, B, x.shape[2:], self._scale, pair=self._pair)
+        s_in = x.new_ones([B])
+        steps = list(self.get_sigma_gen(num_sigmas, init_step=init_step))
+        losses = torch.zeros((len(steps), B), dtype=torch.float32, device=x.device) if record_losses else None
+        slot = 0                                                           # the k-th churned step reads draw k
+        for k, i in enumerate(steps):
+            (e,) = self.step_plan(sig, i, init_step)
+            alpha = 20 * np.sqrt(scales[i])
+            iter_enabled = i in iter_lst
+            thres = float(thres_lst[list(iter_lst).index(i)]) if iter_enabled else 0.0
+            if e.churn != 0.0:
+                ops.axpy_(x, noise[slot], e.churn)
+                slot += 1
+            x, _ = self.attend_and_excite_rows(x, model, s_in * e.sigma, cond, batch, alpha, iter_enabled, thres)
+            stepper.step(x, e.sigma, e.sigma_next, emit_maps=record_losses)
+            if record_losses:
+                losses[k].copy_(model.loss_fn.get_min_local_loss(stepper.unet.attn_map_cache, batch["mask"], batch["seg_mask"],
+                                                                 cond_only=self._pair))
+        if record_losses:
+            stepper.unet.clear_attn_map()
+        stepper.check()
+        if record_losses:
+            self.last_row_losses = losses.cpu()
+        return x
+
     # ------------------------------------------------------------------------------------------- API step
     def sampler_step(self, sigma, next_sigma, model, x, cond, batch=None, uc=None, gamma=0.0, alpha=0, iter_enabled=False,
                      thres=None, update=False, name=None, save_loss=False, save_attn=False, save_inter=False):
