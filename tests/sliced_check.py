@@ -39,8 +39,8 @@ def _f64(t):
     return torch.as_tensor(t).detach().double().cpu()
 
 
-def _report(line):
-    path = REPORT
+def _report(line, report=None):
+    path = REPORT if report is None else report
     if path is None:
         import test_backward_gpu
         path = test_backward_gpu.REPORT
@@ -96,7 +96,8 @@ def block_slices(n, step=16):
 
 
 # ------------------------------------------------------------------------------------------------ the sliced check
-def check_sliced(name, got, ref64, floor_err, slices, *, abs_scale=None, margin_rms=2.0, margin_max=4.0):
+def check_sliced(name, got, ref64, floor_err, slices, *, abs_scale=None, margin_rms=2.0, margin_max=4.0, report=None):
+    """report: a file of its own for this call's line (default: the module's REPORT, see above)"""
     got, ref, floor = _f64(got), _f64(ref64), _f64(floor_err)
     assert got.shape == ref.shape == floor.shape, f"{name}: shapes {tuple(got.shape)} {tuple(ref.shape)} {tuple(floor.shape)}"
     assert bool(torch.isfinite(got).all()), f"{name}: non-finite values in the result"
@@ -146,12 +147,12 @@ def check_sliced(name, got, ref64, floor_err, slices, *, abs_scale=None, margin_
                 failures.append(f"slice {_fmt(idx)} ({n} elements): {kind} error {val:.3e} > bound {bound:.3e}")
     rel = float(err.pow(2).mean().sqrt() / ref.pow(2).mean().sqrt().clamp_min(1e-300))
     _report(f"{name:55s} sliced: {len(merged)} slices, worst {_fmt(worst_idx) if worst_idx is not None else '-'} {worst_kind} "
-            f"ratio-to-bound {worst:.3f}, global rel_rms {rel:.3e}{'  FAIL' if failures else ''}")
+            f"ratio-to-bound {worst:.3f}, global rel_rms {rel:.3e}{'  FAIL' if failures else ''}", report)
     assert not failures, f"{name}: {len(failures)} of {len(merged)} slices out of bound; first: " + "; ".join(failures[:3])
     return worst
 
 
-def check_fp32_sum(name, got, ref64, abs_sum, *, units=FP32_SUM_UNITS):
+def check_fp32_sum(name, got, ref64, abs_sum, *, units=FP32_SUM_UNITS, report=None):
     """fp32 result of a sum of exact products: |got - ref64| <= units * 2^-24 * sum|summands| element by element (an element whose
     summands are all zero must be exactly zero).  Returns the worst |err| / sum|summands| in units of 2^-24."""
     got, ref, asum = _f64(got), _f64(ref64), _f64(abs_sum)
@@ -166,7 +167,7 @@ def check_fp32_sum(name, got, ref64, abs_sum, *, units=FP32_SUM_UNITS):
     rel = float((got - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt().clamp_min(1e-300))
     at = tuple(int(i) for i in torch.unravel_index(ratio.argmax(), ratio.shape)) if ratio.numel() else ()
     _report(f"{name:55s} fp32 sum: worst |err| / sum|summands| = {worst:.2f} x 2^-24 at {at} (bound {units:g}), "
-            f"global rel_rms {rel:.3e}{'  FAIL' if bool(bad.any()) else ''}")
+            f"global rel_rms {rel:.3e}{'  FAIL' if bool(bad.any()) else ''}", report)
     assert not bool(bad.any()), (f"{name}: {int(bad.sum())} of {bad.numel()} elements beyond {units:g} x 2^-24 x sum|summands|; worst "
                                  f"{worst:.2f} units at {at}: got {float(got[at]):.9g}, ref {float(ref[at]):.9g}")
     return worst
