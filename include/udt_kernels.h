@@ -42,6 +42,8 @@
  *   udt_embed_tokens    nn.Embedding + PositionalEncoding  sgm/modules/encoders/modules.py:1069-1085,1160-1163
  *   udt_timestep_embedding  timestep_embedding  sgm/modules/diffusionmodules/util.py:206-230
  *   udt_mask_downsample SpatialRescaler (bilinear x0.125)  sgm/modules/encoders/modules.py:843-857
+ *   udt_crop_resize_aa_f32  the OCR scorer's input side, every box of every image in one launch: the crop results[i, :, t:b, l:r]
+ *                       (test.py:81) + Resize(BICUBIC, antialias=True) + Normalize(0.5, 0.5)  sgm/modules/predictors/model.py:24-29
  *   udt_local_loss_maps head-mean + 3x3 blur + masked max of t_attn maps  sgm/modules/diffusionmodules/loss.py:192-235
  *   the reverse pass (round 6; torch.autograd under attend_and_excite, sgm/modules/diffusionmodules/sampling.py:233-252, and under
  *   DiffusionEngine.training_step, sgm/models/diffusion.py:138-172 with loss.py:131-176,237-286):
@@ -653,6 +655,21 @@ int udt_axpy_f32(float* x, const float* y, float a, int64_t n, void* stream);
  * x / grad not 16-byte aligned, B > 1024.  Nothing is launched in either case. */
 int udt_aae_row_update_f32(float* x, const float* grad, const float* loss, const int32_t* state_in, int32_t* state_out, int32_t* n_active,
                            int32_t B, int64_t n, float alpha, float thres, int32_t iter_enabled, int32_t max_iter, void* stream);
+/* Crop + antialiased bicubic resize + normalise of N boxes in one launch (test.py:81 + the OCR predictor's transform,
+ * sgm/modules/predictors/model.py:24-29): for box n = (image index, top, bottom, left, right), half-open as the slice
+ * img[index, :, top:bottom, left:right],
+ *   out[n] = mul * F.interpolate(crop[None], size=(out_h, out_w), mode="bicubic", antialias=True, align_corners=False) + add
+ * ((mul, add) = (2, -1) is Normalize(0.5, 0.5)).  img fp32 [B, C, H, W], boxes DEVICE int32 [N, 5], out fp32 [N, C, out_h, out_w], all
+ * contiguous.  Separable; along an axis of n_in input and n_out output samples, output i uses scale = n_in / n_out,
+ * support = 2 scale and inv = 1 / scale when scale >= 1 (else 2 and 1), centre = scale (i + 0.5), the taps
+ * lo = max(0, int(centre - support + 0.5)) <= j < hi = min(n_in, int(centre + support + 0.5)) and the weights
+ * k((j - centre + 0.5) inv) divided by their sum, k the Keys cubic with a = -0.5.  Taps clamp at the BOX: no pixel outside it reaches out.
+ * Tap positions and weights are evaluated in fp64 and rounded to fp32 once; products and sums are fp32.
+ * The kernel clamps each box to the image (and to at least one pixel), so it reads no address outside img whatever boxes holds; callers
+ * validate boxes on the host.  No workspace, no host read: the grid depends on (N, C, out_h, out_w) only, and box sizes are unbounded.
+ * UDT_ERR_BAD_ARG: a null pointer; UDT_ERR_BAD_SHAPE: a dimension < 1, C or N > 65535.  Nothing is launched in either case. */
+int udt_crop_resize_aa_f32(const float* img, const int32_t* boxes, float* out, int B, int C, int H, int W, int N, int out_h, int out_w,
+                           float mul, float add, void* stream);
 /* x bf16 += y bf16 (n elements, n % 8 == 0) ; utility for residuals outside GEMM epilogues */
 int udt_add_bf16(void* x, const void* y, int64_t n, void* stream);
 

@@ -1,0 +1,176 @@
+// resample.hip — the OCR scorer's input side: crop + antialiased bicubic resize + normalise, every box of every image in ONE launch.
+//
+//   udt_crop_resize_aa_f32 : test.py:81 (results[i, :, top:bottom, left:right]) + sgm/modules/predictors/model.py:24-29
+//                            (torchvision Resize(BICUBIC, antialias=True) + Normalize(0.5, 0.5)), i.e. per box
+//                            F.interpolate(crop[None], size, mode="bicubic", antialias=True, align_corners=False) * mul + add
+//
+// The resample is separable.  Along an axis of n_in input and n_out output samples, output i takes the taps
+// lo <= j < hi with weight k((j - centre + 0.5) * inv) / (their sum), k the Keys cubic with a = -0.5 (ATen's value when antialiasing).
+//
+// Launch plan.  boxes is device data, so the grid is a function of (N, C, out_h, out_w) alone: one workgroup per
+// (box, channel, 32 x 32 tile of the OUTPUT).  A box is unbounded up to the image, so neither it nor its row-resampled intermediate is
+// assumed to fit in LDS: the workgroup walks the input rows its 32 output rows need in chunks of 64, resamples a chunk horizontally
+// into its 32 output columns (64 x 32 fp32 = 8 KiB of LDS), and adds the chunk's share of the vertical pass to 4 accumulators per
+// thread before the next chunk overwrites it.  No workspace, no host read, no allocation.
+// Tap positions and the cubic are evaluated in fp64 (a tap's offset is a difference of two numbers as large as the box: in fp32 its
+// cancellation error, times the cubic's slope, is larger than the whole fp32 accumulation error); the normalised weight is rounded to
+// fp32 once, and products and sums are fp32.  A weight is evaluated once per 8 rows (horizontal) / once per tap (vertical).
+#include "common.h"
+
+namespace {
+
+constexpr int RS_COLS = 32;      // output columns of a workgroup's tile (the lanes of half a wave: 128-byte row segments)
+constexpr int RS_ROWS = 32;      // output rows of a tile
+constexpr int RS_GROUPS = 8;     // 256 threads = 32 columns x 8 row groups
+constexpr int RS_CHUNK = 64;     // input rows resampled horizontally per pass
+constexpr int RS_RPT = RS_CHUNK / RS_GROUPS;       // input rows per thread and chunk (8)
+constexpr int RS_OPT = RS_ROWS / RS_GROUPS;        // outputs per thread (4)
+
+struct RsAxis {                  // one axis of one box: n_in samples -> n_out
+  double scale, support, inv;
+};
+UDT_DEVINL RsAxis rs_axis(int n_in, int n_out) {
+  RsAxis a;
+  a.scale = (double)n_in / (double)n_out;
+  a.support = a.scale >= 1.0 ? 2.0 * a.scale : 2.0;
+  a.inv = a.scale >= 1.0 ? 1.0 / a.scale : 1.0;
+  return a;
+}
+UDT_DEVINL double rs_centre(const RsAxis& a, int i) {
+#pragma clang fp contract(off)      // (the product is rounded before the support is subtracted: tap ranges as the float64 restatement)
+  return a.scale * ((double)i + 0.5);
+}
+UDT_DEVINL int rs_lo(const RsAxis& a, double centre) { return max(0, (int)(centre - a.support + 0.5)); }
+UDT_DEVINL int rs_hi(const RsAxis& a, double centre, int n_in) { return min(n_in, (int)(centre + a.support + 0.5)); }
+// Keys cubic, a = -0.5
+UDT_DEVINL double rs_cubic(double x) {
+  const double ax = fabs(x);
+  if (ax < 1.0) return (1.5 * ax - 2.5) * ax * ax + 1.0;
+  if (ax < 2.0) return -0.5 * (((ax - 5.0) * ax + 8.0) * ax - 4.0);
+  return 0.0;
+}
+// 1 / (sum of the raw weights of taps [lo, hi)); d0 = lo + 0.5 - centre
+UDT_DEVINL double rs_rsum(double d0, double inv, int ntap) {
+  double s = 0.0;
+  for (int t = 0; t < ntap; ++t) s += rs_cubic((d0 + (double)t) * inv);
+  return 1.0 / s;
+}
+
+__global__ void __launch_bounds__(256) crop_resize_aa_kernel(const float* __restrict__ img, const int32_t* __restrict__ boxes,
+                                                             float* __restrict__ out, int B, int C, int H, int W, int out_h, int out_w,
+                                                             int tiles_x, float mul, float add) {
+  __shared__ float tmp[RS_CHUNK][RS_COLS];
+  __shared__ int s_ylo[RS_ROWS], s_yhi[RS_ROWS];
+  __shared__ double s_yd0[RS_ROWS], s_yrs[RS_ROWS];
+
+  const int n = blockIdx.z, c = blockIdx.y;
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int lx = threadIdx.x & (RS_COLS - 1), g = threadIdx.x >> 5;
+  const int ox = tx * RS_COLS + lx, oy0 = ty * RS_ROWS;
+
+  // the box, clamped to the image and to at least one pixel: whatever boxes holds, every address read lies inside img
+  const int32_t* bx = boxes + (long long)n * 5;
+  const int b = min(max(bx[0], 0), B - 1);
+  const int top = min(max(bx[1], 0), H - 1), bottom = min(max(bx[2], top + 1), H);
+  const int left = min(max(bx[3], 0), W - 1), right = min(max(bx[4], left + 1), W);
+  const int bh = bottom - top, bw = right - left;
+  const float* src = img + (((long long)b * C + c) * H + top) * (long long)W + left;     // pixel (0, 0) of the box
+
+  // vertical tap tables of the tile's 32 output rows (shared by the 32 columns)
+  const RsAxis ay = rs_axis(bh, out_h);
+  if (threadIdx.x < RS_ROWS) {
+    const int oy = oy0 + (int)threadIdx.x;
+    int lo = 0, hi = 0;
+    double d0 = 0.0, rs = 0.0;
+    if (oy < out_h) {
+      const double cy = rs_centre(ay, oy);
+      lo = rs_lo(ay, cy);
+      hi = rs_hi(ay, cy, bh);
+      d0 = (double)lo + 0.5 - cy;
+      rs = rs_rsum(d0, ay.inv, hi - lo);
+    }
+    s_ylo[threadIdx.x] = lo;
+    s_yhi[threadIdx.x] = hi;
+    s_yd0[threadIdx.x] = d0;
+    s_yrs[threadIdx.x] = rs;
+  }
+  // this thread's column: taps [xlo, xlo + nx) of a box row (nx = 0 for a column past out_w: it loads and stores nothing)
+  const RsAxis ax = rs_axis(bw, out_w);
+  int xlo = 0, nx = 0;
+  double xd0 = 0.0, xrs = 0.0;
+  if (ox < out_w) {
+    const double cx = rs_centre(ax, ox);
+    xlo = rs_lo(ax, cx);
+    nx = rs_hi(ax, cx, bw) - xlo;
+    xd0 = (double)xlo + 0.5 - cx;
+    xrs = rs_rsum(xd0, ax.inv, nx);
+  }
+  __syncthreads();
+
+  // input rows the tile needs: lo and hi grow with the output row
+  const int last = min(RS_ROWS, out_h - oy0) - 1;
+  const int row_begin = s_ylo[0], row_end = s_yhi[last];
+
+  float vacc[RS_OPT];
+#pragma unroll
+  for (int m = 0; m < RS_OPT; ++m) vacc[m] = 0.f;
+
+  for (int r0 = row_begin; r0 < row_end; r0 += RS_CHUNK) {
+    // horizontal pass: rows r0 + g + 8 k (k = 0..7) of the box into this thread's column; a row past the tile's range repeats the
+    // last one (an address inside the box) and is not read back below
+    const float* rp[RS_RPT];
+    float hacc[RS_RPT];
+#pragma unroll
+    for (int k = 0; k < RS_RPT; ++k) {
+      rp[k] = src + (long long)min(r0 + g + RS_GROUPS * k, row_end - 1) * W + xlo;
+      hacc[k] = 0.f;
+    }
+    for (int t = 0; t < nx; ++t) {
+      const float w = (float)(rs_cubic((xd0 + (double)t) * ax.inv) * xrs);
+#pragma unroll
+      for (int k = 0; k < RS_RPT; ++k) hacc[k] = __builtin_fmaf(w, rp[k][t], hacc[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < RS_RPT; ++k) tmp[g + RS_GROUPS * k][lx] = hacc[k];
+    __syncthreads();
+    // vertical pass over the chunk: output rows oy0 + g + 8 m (m = 0..3)
+    const int r1 = min(r0 + RS_CHUNK, row_end);
+#pragma unroll
+    for (int m = 0; m < RS_OPT; ++m) {
+      const int q = g + RS_GROUPS * m;
+      const int lo = s_ylo[q];
+      const int a = max(lo, r0), e = min(s_yhi[q], r1);
+      const double d0 = s_yd0[q], rs = s_yrs[q];
+      for (int r = a; r < e; ++r) {
+        const float w = (float)(rs_cubic((d0 + (double)(r - lo)) * ay.inv) * rs);
+        vacc[m] = __builtin_fmaf(w, tmp[r - r0][lx], vacc[m]);
+      }
+    }
+    __syncthreads();       // (the next chunk overwrites tmp)
+  }
+
+  if (ox < out_w) {
+    float* dst = out + (((long long)n * C + c) * out_h) * (long long)out_w + ox;
+#pragma unroll
+    for (int m = 0; m < RS_OPT; ++m) {
+      const int oy = oy0 + g + RS_GROUPS * m;
+      if (oy < out_h) dst[(long long)oy * out_w] = __builtin_fmaf(mul, vacc[m], add);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int udt_crop_resize_aa_f32(const float* img, const int32_t* boxes, float* out, int B, int C, int H, int W, int N, int out_h,
+                                      int out_w, float mul, float add, void* stream) {
+  if (!img || !boxes || !out) return UDT_ERR_BAD_ARG;
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || N <= 0 || out_h <= 0 || out_w <= 0) return UDT_ERR_BAD_SHAPE;
+  const long long tiles_x = (out_w + RS_COLS - 1) / RS_COLS, tiles_y = (out_h + RS_ROWS - 1) / RS_ROWS;
+  if (tiles_x * tiles_y > 0x7fffffffLL || C > 65535 || N > 65535) return UDT_ERR_BAD_SHAPE;      // grid limits
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  UdtProfScope prof(5, s);
+  hipLaunchKernelGGL(crop_resize_aa_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)C, (unsigned)N), dim3(256), 0, s, img, boxes, out,
+                     B, C, H, W, out_h, out_w, (int)tiles_x, mul, add);
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}

@@ -952,6 +952,22 @@ def mask_downsample(mask: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def crop_resize_aa(img: torch.Tensor, boxes: torch.Tensor, out_hw, mul: float = 1.0, add: float = 0.0) -> torch.Tensor:
+    """crop + antialiased bicubic resize + ``mul * v + add`` of every box in one launch (udt_crop_resize_aa_f32): img fp32
+    [B, C, H, W]; boxes DEVICE int32 [N, 5] = (image index, top, bottom, left, right), half-open as the slice
+    img[index, :, top:bottom, left:right]; -> fp32 [N, C, oh, ow].  The kernel clamps a box to the image; validating boxes is
+    the caller's, on the host (ParseqPredictor.transform_boxes)."""
+    assert img.dtype == torch.float32 and img.dim() == 4 and img.is_contiguous()
+    assert boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] == 5 and boxes.is_contiguous()
+    assert boxes.device == img.device
+    B, Cc, H, W_ = img.shape
+    N, (oh, ow) = boxes.shape[0], (int(v) for v in out_hw)
+    out = torch.empty((N, Cc, oh, ow), dtype=torch.float32, device=img.device)
+    L.check(L.load().udt_crop_resize_aa_f32(_ptr(img), _ptr(boxes), _ptr(out), B, Cc, H, W_, N, oh, ow, float(mul), float(add), _stream()),
+            "udt_crop_resize_aa_f32")
+    return out
+
+
 def local_loss_accumulate(probs: torch.Tensor, mask: torch.Tensor, seg_mask: torch.Tensor, gk9: torch.Tensor,
                           loss: torch.Tensor, heads: int, size: int) -> None:
     """loss [n] += per-layer local-loss term of n = probs.shape[0] / heads samples; sample i is scored against

@@ -315,3 +315,69 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
         sampler.release_retired()
     del keep
     return out
+
+
+def _host_boxes(batch: dict, k: int):
+    """(labels, [B, 4] int64 host boxes) of batch k, validated against its image size"""
+    if "r_bbox" not in batch:
+        raise ValueError(f"batch {k} has no r_bbox: evaluate needs the text box of every image")
+    if "label" not in batch:
+        raise ValueError(f"batch {k} has no label")
+    rb = batch["r_bbox"]
+    if isinstance(rb, torch.Tensor) and rb.is_cuda:
+        raise ValueError(f"batch {k}: r_bbox is on the GPU; evaluate reads box values on the host only")
+    rb = torch.as_tensor(rb).reshape(-1, 4).to(torch.int64)
+    labels = list(batch["label"])
+    if rb.shape[0] != len(labels):
+        raise ValueError(f"batch {k}: {rb.shape[0]} boxes for {len(labels)} labels")
+    H, W = _image_hw(batch)
+    for i, (t, b, l, r) in enumerate(rb.tolist()):
+        if not (0 <= t < b <= H and 0 <= l < r <= W):
+            raise ValueError(f"batch {k}, image {i}: box rows {t}:{b}, columns {l}:{r} does not lie in its {H} x {W} image")
+    return labels, rb
+
+
+@torch.no_grad()
+def evaluate(cfgs, model, sampler, batches, predictor, device: Optional[torch.device] = None, in_flight: Optional[int] = None,
+             fuse: Optional[int] = None, image_seeds: Optional[list] = None, ocr_batch: Optional[int] = 64,
+             return_samples: bool = False) -> dict:
+    """reference test.py:74-91 in throughput mode: generate with ``predict_many``, read the text back with the OCR predictor, count
+    the exact matches — the sequence accuracy UDiffText is judged by.
+    Every batch carries ``label`` (one string per image) and ``r_bbox`` ([B, 4] host integers: top, bottom, left, right of the text
+    box, the slice results[i, :, top:bottom, left:right] of test.py:81).  Labels and boxes are taken, and the boxes validated against the
+    batch's image size, on the HOST before anything is sampled (ValueError; a batch without r_bbox is one) — box values are never
+    read back from the GPU.  ``predict_many`` then runs unchanged (``in_flight``, ``fuse``, ``image_seeds``, cfgs.aae_enabled as
+    there).  Each returned batch's boxes are cropped, resized and normalised in one launch (``predictor.transform_boxes``); the crops
+    are concatenated in input order and read in consecutive chunks of at most ``ocr_batch`` (``predictor.txt_of``: one autoregressive
+    decoding loop per chunk); ``ocr_batch=None``: one chunk per input batch, the reference's grouping.  An image is correct when
+    pred.lower() == label.lower() (test.py:84).
+    -> {"accuracy", "correct", "total", "pred": [[str]], "label": [[str]]} (per batch, input order) and, with ``return_samples``,
+    "outputs": the ``predict_many`` list.  ``predictor`` is duck-typed: only ``transform_boxes`` and ``txt_of`` are used.
+    One device only: under data parallelism each rank calls ``evaluate`` on its shard and the ranks add up "correct" and "total"."""
+    if ocr_batch is not None and int(ocr_batch) < 1:
+        raise ValueError(f"ocr_batch must be a positive count or None, not {ocr_batch!r}")
+    labels, boxes = [], []
+    for k, batch in enumerate(batches):
+        lb, rb = _host_boxes(batch, k)
+        labels.append(lb)
+        boxes.append(torch.cat((torch.arange(rb.shape[0]).reshape(-1, 1), rb), 1))       # + the image's index in its batch
+    outputs = predict_many(cfgs, model, sampler, batches, device, in_flight=in_flight, fuse=fuse, image_seeds=image_seeds)
+    crops = [predictor.transform_boxes(samples, bx) for (samples, _), bx in zip(outputs, boxes)]
+    if ocr_batch is None:
+        chunks = crops
+    else:
+        flat = torch.cat(crops, 0) if crops else None
+        chunks = [flat[i:i + int(ocr_batch)] for i in range(0, flat.shape[0] if crops else 0, int(ocr_batch))]
+    flat_pred = [t for x in chunks if x.shape[0] for t in predictor.txt_of(x)]
+    total = sum(len(lb) for lb in labels)
+    if len(flat_pred) != total:
+        raise RuntimeError(f"the predictor returned {len(flat_pred)} strings for {total} crops")
+    pred, o = [], 0
+    for lb in labels:
+        pred.append(flat_pred[o:o + len(lb)])
+        o += len(lb)
+    correct = sum(p.lower() == t.lower() for ps, ls in zip(pred, labels) for p, t in zip(ps, ls))
+    res = {"accuracy": correct / total if total else 0.0, "correct": int(correct), "total": int(total), "pred": pred, "label": labels}
+    if return_samples:
+        res["outputs"] = outputs
+    return res

@@ -368,6 +368,35 @@ class ParseqPredictor(nn.Module):
         label, _ = self.parseq.tokenizer.decode(self(x))
         return label
 
+    # ---- box-based entry points (pipeline.evaluate): the crops stay on the device as boxes of the sample batch, and all of them
+    # are resampled in ONE launch (udt_crop_resize_aa_f32) instead of one F.interpolate per sliced crop as in ``transform``
+    def transform_boxes(self, samples, boxes):
+        """samples fp32 [B, 3, H, W] in [0, 1] on the GPU (what ``predict`` returns); boxes: a HOST int tensor or list [N, 5] =
+        (image index, top, bottom, left, right), half-open as samples[index, :, top:bottom, left:right] (test.py:81)
+        -> the normalised PARSeq input fp32 [N, 3, h, w] (hparams.img_size).  Boxes are validated here, on the host."""
+        from udifftext_amd import ops
+        if isinstance(boxes, torch.Tensor) and boxes.is_cuda:
+            raise ValueError("transform_boxes takes boxes on the host (their values are validated before the launch)")
+        bx = torch.as_tensor(boxes).reshape(-1, 5)
+        if bx.is_floating_point() or bx.dtype == torch.bool:
+            raise ValueError(f"boxes must be integers, not {bx.dtype}")
+        bx = bx.to(torch.int64)
+        B, _, H, W = samples.shape
+        for n, (i, t, b, l, r) in enumerate(bx.tolist()):
+            if not (0 <= i < B and 0 <= t < b <= H and 0 <= l < r <= W):
+                raise ValueError(f"box {n} = (image {i}, rows {t}:{b}, columns {l}:{r}) does not lie in a batch of {B} images of {H} x {W}")
+        if bx.shape[0] == 0:
+            return samples.new_empty((0, samples.shape[1]) + tuple(self.parseq.hparams.img_size), dtype=torch.float32)
+        dev_boxes = bx.to(torch.int32).to(samples.device)
+        return ops.crop_resize_aa(samples.float().contiguous(), dev_boxes, self.parseq.hparams.img_size, mul=2.0, add=-1.0)
+
+    def txt_of(self, x):
+        """x: the normalised input [N, 3, h, w] (``transform_boxes`` / ``transform``) -> the decoded strings"""
+        return self.parseq.tokenizer.decode(self.parseq(x))[0]
+
+    def img2txt_boxes(self, samples, boxes):
+        return self.txt_of(self.transform_boxes(samples, boxes))
+
     def calc_loss(self, x, label):
         preds = self(x)
         gt_ids = self.parseq.tokenizer.encode(label).to(preds.device)
