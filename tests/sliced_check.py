@@ -95,6 +95,45 @@ def block_slices(n, step=16):
         yield (slice(i0, min(n, i0 + step)),)
 
 
+def gemm_tile_slices(M, N, bm, bn, wr, wc, batch=None):
+    """[M, N] (or [batch, M, N]): (M-tile, N-tile, wave row block of wr rows, wave column block of wc columns) of a bm x bn tiled GEMM,
+    clipped at the ragged M and N tails — one wave's outputs of one tile"""
+    for b in ([None] if batch is None else range(batch)):
+        for m0 in range(0, M, bm):
+            for n0 in range(0, N, bn):
+                for r0 in range(m0, min(M, m0 + bm), wr):
+                    for c0 in range(n0, min(N, n0 + bn), wc):
+                        idx = (slice(r0, min(M, m0 + bm, r0 + wr)), slice(c0, min(N, n0 + bn, c0 + wc)))
+                        yield idx if b is None else (b,) + idx
+
+
+def conv_tile_slices(B, H, W, N, th, tw, bn, step=1):
+    """[B, H, W, N] (NHWC output): (image, tile y, tile x, N-tile) of a convolution cut into th x tw pixel tiles and bn-column tiles;
+    step 2: the phase form, whose tile of the low-resolution map owns the 2 th x 2 tw output pixels above it"""
+    th, tw = th * step, tw * step
+    for b in range(B):
+        for y0 in range(0, H, th):
+            for x0 in range(0, W, tw):
+                for n0 in range(0, N, bn):
+                    yield (b, slice(y0, min(H, y0 + th)), slice(x0, min(W, x0 + tw)), slice(n0, min(N, n0 + bn)))
+
+
+def ring_slices(B, H, W):
+    """[B, H, W, N]: each image's outer pixel ring (top row, bottom row, left and right columns) apart from its interior; the rings of
+    all images come first so that merging short units never joins a ring to an interior"""
+    for b in range(B):
+        yield (b, slice(0, 1), slice(0, W), slice(None))
+        if H > 1:
+            yield (b, slice(H - 1, H), slice(0, W), slice(None))
+        if H > 2:
+            yield (b, slice(1, H - 1), slice(0, 1), slice(None))
+            if W > 1:
+                yield (b, slice(1, H - 1), slice(W - 1, W), slice(None))
+    for b in range(B):
+        if H > 2 and W > 2:
+            yield (b, slice(1, H - 1), slice(1, W - 1), slice(None))
+
+
 # ------------------------------------------------------------------------------------------------ the sliced check
 def check_sliced(name, got, ref64, floor_err, slices, *, abs_scale=None, margin_rms=2.0, margin_max=4.0, report=None):
     """report: a file of its own for this call's line (default: the module's REPORT, see above)"""
