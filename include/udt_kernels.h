@@ -59,6 +59,12 @@
  *                                                         LitEma.store / copy_to / restore (ema.py:56-86), one launch each
  *     udt_aae_row_update_f32                              the attend-and-excite update and exit rule (sampling.py:247-250), row by row
  *     (backward-data of linears and convolutions: udt_gemm on re-packed weights)
+ *   the OCR loss on decoded frames and its gradient (FullLoss.get_ocr_loss, loss.py:178-190; ParseqPredictor.calc_loss,
+ *   sgm/modules/predictors/model.py:40-58, under torch.autograd):
+ *     udt_ocr_ce_f32                                      F.cross_entropy over the label's characters + clamp(max=1), with its seed
+ *     udt_mattn_bwd                                       autograd of udt_mattn_fwd (ViT self-attention, decoder cross-attention)
+ *     udt_gelu_fwd / udt_gelu_bwd                         nn.GELU of the ViT / decoder MLPs on stored pre-activations
+ *     udt_crop_resize_aa_bwd_f32                          autograd of udt_crop_resize_aa_f32
  *
  * Conventions
  *   - every pointer is a DEVICE pointer owned by the caller; kernels borrow it for the stream-ordered
@@ -670,6 +676,64 @@ int udt_aae_row_update_f32(float* x, const float* grad, const float* loss, const
  * UDT_ERR_BAD_ARG: a null pointer; UDT_ERR_BAD_SHAPE: a dimension < 1, C or N > 65535.  Nothing is launched in either case. */
 int udt_crop_resize_aa_f32(const float* img, const int32_t* boxes, float* out, int B, int C, int H, int W, int N, int out_h, int out_w,
                            float mul, float add, void* stream);
+/* The adjoint of udt_crop_resize_aa_f32 (its backward with respect to img; `add` has no part in it):
+ *   d_img[b, c, y, x] = mul * sum_oy sum_ox wy(oy, y - top) wx(ox, x - left) d_out[n, c, oy, ox]
+ * for the box n of image b and (y, x) inside it, with the forward's tap rule and the forward's weights (the same device functions:
+ * tap positions and weights evaluated in fp64, each weight rounded to fp32 once).  d_out fp32 [N, C, out_h, out_w], boxes DEVICE int32
+ * [N, 5] as in the forward, d_img fp32 [B, C, H, W], all contiguous.
+ * EVERY element of d_img is written exactly once: zero outside the boxes and for images without a box — the caller clears nothing.
+ * Precondition: every image index appears in at most one box (one box per image, loss.py:184; the Python wrapper validates it on the
+ * host).  Given a table that breaks it, the FIRST box of an image is used and the others are ignored: no address outside d_img is
+ * touched.  Boxes are clamped to the image exactly as the forward clamps them.
+ * Gather form, no atomics: the outputs that read an input sample are one contiguous range per axis; per input pixel, for every output
+ * column ox in ascending order, inner = sum over oy ascending of wy * d_out (fp32 FMA), acc += wx * inner (fp32 FMA); the result is
+ * mul * acc, rounded once more.  Bit-identical from run to run.  The grid depends on (B, C, H, W) only; no workspace, no host read.
+ * UDT_ERR_BAD_ARG: a null pointer; UDT_ERR_BAD_SHAPE: a dimension < 1, H, B * C or N > 65535.  Nothing is launched in either case. */
+int udt_crop_resize_aa_bwd_f32(const float* d_out, const int32_t* boxes, float* d_img, int B, int C, int H, int W, int N, int out_h,
+                               int out_w, float mul, void* stream);
+/* Backward of udt_mattn_fwd: same operands and layout (q, k, v bf16 row views with their ld and batch strides, optional fp32 additive
+ * mask [nq, ldmask], optional uint8 kpm [batch, lk]) plus
+ *   d_o : bf16 rows (b, i) at d_o + b*do_bstride + i*lddo + h*head_dim, the cotangent of o
+ *   dq  : bf16 rows (b, i) at dq + b*dq_bstride + i*lddq + h*head_dim, or NULL (not wanted: the decoder's queries are constants)
+ *   dk, dv : bf16 rows (b, l) at dk + b*dk_bstride + l*lddk + h*head_dim (dv likewise)
+ * Only the heads*head_dim columns of a row are written; ld gaps are neither read nor written.
+ * Domain: that of the forward (head_dim % 8 == 0, head_dim <= 64, lk <= 256, lk*head_dim <= 8192, batch <= 65535) and
+ * nq*head_dim <= 8192; every ld >= heads*head_dim.
+ * The forward stores no log-sum-exp: scores, softmax P, dP = dO V^T, delta_i = sum_l P_il dP_il and dS = P (dP - delta) are recomputed
+ * in fp32 from the bf16 operands, then dv = P^T dO, dk = scale dS^T Q, dq = scale dS K with fp32 accumulation (query rows / keys in
+ * ascending order).  ROUNDING: the only values rounded below fp32 are the stored dq, dk, dv (bf16, round to nearest even, once each);
+ * P and dS are never rounded to bf16.  A query whose keys are all masked has P = 0: it contributes nothing to dk / dv and gets dq = 0,
+ * matching the forward's zeros.  One workgroup per (head, sample), no atomics: bit-identical from run to run.
+ * UDT_ERR_BAD_ARG: a null pointer other than dq / mask / kpm; UDT_ERR_BAD_SHAPE: outside the domain.  Nothing is launched in either case. */
+int udt_mattn_bwd(const void* q, const void* k, const void* v, const void* d_o, void* dq, void* dk, void* dv, const float* mask,
+                  const uint8_t* kpm, int32_t batch, int32_t heads, int32_t head_dim, int32_t nq, int32_t lk,
+                  int32_t ldq, int32_t ldk, int32_t ldv, int32_t lddo, int32_t lddq, int32_t lddk, int32_t lddv, int32_t ldmask,
+                  int64_t q_bstride, int64_t k_bstride, int64_t v_bstride, int64_t do_bstride, int64_t dq_bstride, int64_t dk_bstride,
+                  int64_t dv_bstride, float scale, void* stream);
+/* Exact-erf GELU (nn.GELU / F.gelu default) on STORED pre-activations a fp32 [rows, C] contiguous, C % 8 == 0 (the inference path's
+ * GEMM epilogue keeps none; fp32 = the GEMM's accumulators under UDT_GEMM_OUT_F32, so the tape-mode forward rounds where the fused
+ * epilogue rounds): out bf16 [rows, C] = gelu(a); backward: dy bf16 [rows, C] -> da bf16 [rows, C] = dy * (Phi(a) + a phi(a)).
+ * fp32 arithmetic (erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7); ROUNDING: the stored out / da only (bf16, once).
+ * da may alias dy.
+ * UDT_ERR_BAD_ARG: a null pointer; UDT_ERR_BAD_SHAPE: rows < 1, C < 1, C % 8 != 0.  Nothing is launched in either case. */
+int udt_gelu_fwd(const void* a, void* out, int64_t rows, int32_t C, void* stream);
+int udt_gelu_bwd(const void* a, const void* dy, void* da, int64_t rows, int32_t C, void* stream);
+/* The OCR loss of N rows and its seed in one launch (ParseqPredictor.calc_loss, sgm/modules/predictors/model.py:40-58):
+ *   logits  fp32 [N, L, ld], the first n_cls columns of a row are the classes (n_cls <= 256, L <= 256)
+ *   targets int32 [N, T], n_chars int32 [N] with 1 <= n_chars[b] <= min(L, T) (validated by the caller on the host; the kernel clamps
+ *           both n_chars and the target ids into range, so it reads no address outside a row whatever they hold)
+ *   weight  fp32 [N] or NULL (= 1): the upstream cotangent of each row's loss
+ *   loss[b] = min(1, m_b),  m_b = mean_{t < n} CE(logits[b, t], targets[b, t])          (the characters only, EOS excluded)
+ *   d_logits fp32 [N, L, ld_d]: for rows with m_b <= 1 (torch's clamp rule), d_logits[b, t, c] = weight[b] (softmax_c - onehot_c) / n
+ *           for t < n; ZERO everywhere else — every class of a clamped row and every t >= n.  All n_cls columns of all L positions
+ *           are written (no memset needed); columns n_cls .. ld_d - 1 are not touched.
+ * A NaN cross entropy (a NaN or +inf logit) gives loss[b] = NaN and a zero gradient row (NaN <= 1 is false).
+ * ROUNDING: log-sum-exp, softmax, the mean (characters added in ascending order) are evaluated in fp64 from the fp32 logits; the only
+ * rounding is the conversion of loss[b] and of each d_logits element to fp32.  One workgroup per row, no atomics.
+ * UDT_ERR_BAD_ARG: a null pointer other than weight; UDT_ERR_BAD_SHAPE: N, L, T or n_cls < 1, L or n_cls > 256, ld or ld_d < n_cls.
+ * Nothing is launched in either case. */
+int udt_ocr_ce_f32(const float* logits, const int32_t* targets, const int32_t* n_chars, const float* weight, float* loss,
+                   float* d_logits, int32_t N, int32_t L, int32_t n_cls, int32_t ld, int32_t T, int32_t ld_d, void* stream);
 /* x bf16 += y bf16 (n elements, n % 8 == 0) ; utility for residuals outside GEMM epilogues */
 int udt_add_bf16(void* x, const void* y, int64_t n, void* stream);
 

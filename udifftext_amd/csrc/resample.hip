@@ -55,6 +55,8 @@ UDT_DEVINL double rs_rsum(double d0, double inv, int ntap) {
   for (int t = 0; t < ntap; ++t) s += rs_cubic((d0 + (double)t) * inv);
   return 1.0 / s;
 }
+// normalised weight of tap lo + t, rounded to fp32 once (the forward and the adjoint evaluate this one expression)
+UDT_DEVINL float rs_weight(double d0, double inv, double rsum, int t) { return (float)(rs_cubic((d0 + (double)t) * inv) * rsum); }
 
 __global__ void __launch_bounds__(256) crop_resize_aa_kernel(const float* __restrict__ img, const int32_t* __restrict__ boxes,
                                                              float* __restrict__ out, int B, int C, int H, int W, int out_h, int out_w,
@@ -126,7 +128,7 @@ __global__ void __launch_bounds__(256) crop_resize_aa_kernel(const float* __rest
       hacc[k] = 0.f;
     }
     for (int t = 0; t < nx; ++t) {
-      const float w = (float)(rs_cubic((xd0 + (double)t) * ax.inv) * xrs);
+      const float w = rs_weight(xd0, ax.inv, xrs, t);
 #pragma unroll
       for (int k = 0; k < RS_RPT; ++k) hacc[k] = __builtin_fmaf(w, rp[k][t], hacc[k]);
     }
@@ -142,7 +144,7 @@ __global__ void __launch_bounds__(256) crop_resize_aa_kernel(const float* __rest
       const int a = max(lo, r0), e = min(s_yhi[q], r1);
       const double d0 = s_yd0[q], rs = s_yrs[q];
       for (int r = a; r < e; ++r) {
-        const float w = (float)(rs_cubic((d0 + (double)(r - lo)) * ay.inv) * rs);
+        const float w = rs_weight(d0, ay.inv, rs, r - lo);
         vacc[m] = __builtin_fmaf(w, tmp[r - r0][lx], vacc[m]);
       }
     }
@@ -159,7 +161,90 @@ __global__ void __launch_bounds__(256) crop_resize_aa_kernel(const float* __rest
   }
 }
 
+// ---- the adjoint: d_img[b, c, y, x] = mul * sum_oy wy(oy, y - top) sum_ox wx(ox, x - left) d_out[n, c, oy, ox] for the box n of image b
+// Gather form.  The taps [lo, hi) of an axis grow with the output index, so the outputs that read input sample j are one contiguous
+// range [i0, i1): rs_out_range starts below it (from the real-valued inverse of the tap rule, two outputs of slack) and walks up with
+// rs_lo / rs_hi themselves — the range is DEFINED by the forward's rule, not restated.
+UDT_DEVINL void rs_out_range(const RsAxis& a, int n_in, int n_out, int j, int& i0, int& i1) {
+  int i = (int)floor(((double)j - a.support) / a.scale - 0.5) - 2;
+  i = min(max(i, 0), n_out);
+  while (i < n_out && rs_hi(a, rs_centre(a, i), n_in) <= j) ++i;
+  i0 = i;
+  while (i < n_out && rs_lo(a, rs_centre(a, i)) <= j) ++i;
+  i1 = i;
+}
+// weight of input sample j in output i of an axis (j inside i's taps)
+UDT_DEVINL float rs_weight_of(const RsAxis& a, int n_in, int i, int j) {
+  const double c = rs_centre(a, i);
+  const int lo = rs_lo(a, c);
+  const double d0 = (double)lo + 0.5 - c;
+  return rs_weight(d0, a.inv, rs_rsum(d0, a.inv, rs_hi(a, c, n_in) - lo), j - lo);
+}
+
+constexpr int RB_COLS = 256;     // input columns of a workgroup: one row segment of one channel of one image
+
+// Launch plan: one workgroup per (256-column segment, row y, image b * C + c) of d_img — a function of (B, C, H, W) alone.  The
+// workgroup looks the image's box up in the table (the first row whose index is b; none: the segment is zero), its 256 threads
+// evaluate the vertical weights of the outputs that read row y once (LDS, 256 outputs at a time), and every thread inside the box sums
+// its column's outputs: per output column ox, inner = sum_oy wy d_out (ascending oy), acc += wx * inner (ascending ox).
+__global__ void __launch_bounds__(RB_COLS) crop_resize_aa_bwd_kernel(const float* __restrict__ d_out, const int32_t* __restrict__ boxes,
+                                                                     float* __restrict__ d_img, int B, int C, int H, int W, int N,
+                                                                     int out_h, int out_w, float mul) {
+  __shared__ float s_wy[RB_COLS];
+  const int x = blockIdx.x * RB_COLS + (int)threadIdx.x, y = blockIdx.y;
+  const int b = blockIdx.z / C, c = blockIdx.z - b * C;
+  int n = -1;
+  for (int i = 0; i < N; ++i)
+    if (min(max(boxes[(long long)i * 5], 0), B - 1) == b) { n = i; break; }
+  float* dst = d_img + (((long long)b * C + c) * H + y) * (long long)W;
+  int top = 0, bottom = 0, left = 0, right = 0;
+  if (n >= 0) {                                              // clamped exactly as the forward clamps it
+    const int32_t* bx = boxes + (long long)n * 5;
+    top = min(max(bx[1], 0), H - 1); bottom = min(max(bx[2], top + 1), H);
+    left = min(max(bx[3], 0), W - 1); right = min(max(bx[4], left + 1), W);
+  }
+  if (n < 0 || y < top || y >= bottom) {                     // (uniform over the workgroup)
+    if (x < W) dst[x] = 0.f;
+    return;
+  }
+  const int bh = bottom - top, bw = right - left;
+  const RsAxis ay = rs_axis(bh, out_h), ax = rs_axis(bw, out_w);
+  int oy0, oy1;
+  rs_out_range(ay, bh, out_h, y - top, oy0, oy1);
+  const bool inside = x >= left && x < right;                // (x < W follows)
+  int ox0 = 0, ox1 = 0;
+  if (inside) rs_out_range(ax, bw, out_w, x - left, ox0, ox1);
+  const float* src = d_out + ((long long)n * C + c) * out_h * (long long)out_w;
+  float acc = 0.f;
+  for (int c0 = oy0; c0 < oy1; c0 += RB_COLS) {
+    const int cnt = min(RB_COLS, oy1 - c0);
+    __syncthreads();                                         // (the previous chunk's weights are no longer read)
+    if ((int)threadIdx.x < cnt) s_wy[threadIdx.x] = rs_weight_of(ay, bh, c0 + (int)threadIdx.x, y - top);
+    __syncthreads();
+    for (int ox = ox0; ox < ox1; ++ox) {
+      const float wx = rs_weight_of(ax, bw, ox, x - left);
+      float inner = 0.f;
+      for (int k = 0; k < cnt; ++k) inner = __builtin_fmaf(s_wy[k], src[(long long)(c0 + k) * out_w + ox], inner);
+      acc = __builtin_fmaf(wx, inner, acc);
+    }
+  }
+  if (x < W) dst[x] = inside ? mul * acc : 0.f;
+}
+
 }  // namespace
+
+extern "C" int udt_crop_resize_aa_bwd_f32(const float* d_out, const int32_t* boxes, float* d_img, int B, int C, int H, int W, int N,
+                                          int out_h, int out_w, float mul, void* stream) {
+  if (!d_out || !boxes || !d_img) return UDT_ERR_BAD_ARG;
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || N <= 0 || out_h <= 0 || out_w <= 0) return UDT_ERR_BAD_SHAPE;
+  if (H > 65535 || (long long)B * C > 65535 || N > 65535) return UDT_ERR_BAD_SHAPE;      // grid limits
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  UdtProfScope prof(5, s);
+  hipLaunchKernelGGL(crop_resize_aa_bwd_kernel, dim3((unsigned)((W + RB_COLS - 1) / RB_COLS), (unsigned)H, (unsigned)(B * C)),
+                     dim3(RB_COLS), 0, s, d_out, boxes, d_img, B, C, H, W, N, out_h, out_w, mul);
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}
 
 extern "C" int udt_crop_resize_aa_f32(const float* img, const int32_t* boxes, float* out, int B, int C, int H, int W, int N, int out_h,
                                       int out_w, float mul, float add, void* stream) {

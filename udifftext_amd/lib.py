@@ -153,6 +153,12 @@ SYMBOLS = {
     "udt_axpy_f32": (C.c_int, [_fp, _fp, _f32, _i64, _vp]),
     "udt_aae_row_update_f32": (C.c_int, [_fp, _fp, _fp, _vp, _vp, _vp, _i32, _i64, _f32, _f32, _i32, _i32, _vp]),
     "udt_crop_resize_aa_f32": (C.c_int, [_fp, _vp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),
+    "udt_crop_resize_aa_bwd_f32": (C.c_int, [_fp, _vp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "udt_mattn_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _vp, _i32, _i32, _i32, _i32, _i32,
+                                _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp]),
+    "udt_gelu_fwd": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "udt_gelu_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "udt_ocr_ce_f32": (C.c_int, [_fp, _vp, _vp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "udt_center_tokens": (C.c_int, [_fp, _vp, _i32, _i32, _i32, _vp]),
     "udt_transpose_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "udt_reduce_rows_f32": (C.c_int, [_fp, _fp, _i32, _i64, _i32, _vp]),

@@ -968,6 +968,108 @@ def crop_resize_aa(img: torch.Tensor, boxes: torch.Tensor, out_hw, mul: float = 
     return out
 
 
+def crop_resize_aa_bwd(d_out: torch.Tensor, boxes: torch.Tensor, img_shape, mul: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the adjoint of ``crop_resize_aa`` (udt_crop_resize_aa_bwd_f32): d_out fp32 [N, C, oh, ow], the same DEVICE int32 boxes [N, 5]
+    -> d_img fp32 ``img_shape`` = [B, C, H, W], every element written (zero outside the boxes and for images without one).
+    Precondition: an image index appears in at most one box — validated by the caller on the host (``unique_box_images``)."""
+    assert d_out.dtype == torch.float32 and d_out.dim() == 4 and d_out.is_contiguous()
+    assert boxes.dtype == torch.int32 and boxes.dim() == 2 and boxes.shape[1] == 5 and boxes.is_contiguous()
+    assert boxes.device == d_out.device and boxes.shape[0] == d_out.shape[0]
+    B, Cc, H, W_ = (int(v) for v in img_shape)
+    N, oh, ow = d_out.shape[0], d_out.shape[2], d_out.shape[3]
+    assert d_out.shape[1] == Cc
+    if out is None:
+        out = torch.empty((B, Cc, H, W_), dtype=torch.float32, device=d_out.device)
+    assert out.dtype == torch.float32 and out.shape == (B, Cc, H, W_) and out.is_contiguous()
+    L.check(L.load().udt_crop_resize_aa_bwd_f32(_ptr(d_out), _ptr(boxes), _ptr(out), B, Cc, H, W_, N, oh, ow, float(mul), _stream()),
+            "udt_crop_resize_aa_bwd_f32")
+    return out
+
+
+def unique_box_images(boxes) -> None:
+    """host check of ``crop_resize_aa_bwd``'s precondition on a HOST box table [N, 5]: raises ValueError on a repeated image index"""
+    seen = {}
+    for n, row in enumerate(torch.as_tensor(boxes).reshape(-1, 5).tolist()):
+        i = int(row[0])
+        if i in seen:
+            raise ValueError(f"boxes {seen[i]} and {n} both lie in image {i}: the gradient takes one box per image")
+        seen[i] = n
+
+
+def masked_attention_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d_o: torch.Tensor, heads: int, scale: float,
+                         mask: Optional[torch.Tensor] = None, key_padding_mask: Optional[torch.Tensor] = None, want_dq: bool = True,
+                         dq: Optional[torch.Tensor] = None, dk: Optional[torch.Tensor] = None, dv: Optional[torch.Tensor] = None):
+    """backward of ``masked_attention`` (udt_mattn_bwd): the same q / k / v row views and masks, d_o bf16 [B, Nq, *] -> (dq or None,
+    dk, dv) bf16 [B, Nq | Lk, heads*D]; dq / dk / dv may be given as row views (column slices of one [.., 3C] or [.., 2C] buffer)"""
+    _bf16(q); _bf16(k); _bf16(v); _bf16(d_o)
+    B, Nq, Cq = q.shape
+    Lk = k.shape[1]
+    D = Cq // heads
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1 and d_o.stride(2) == 1 and d_o.shape[:2] == (B, Nq)
+    new = lambda n: torch.empty((B, n, heads * D), dtype=torch.bfloat16, device=q.device)
+    if want_dq and dq is None:
+        dq = new(Nq)
+    if not want_dq:
+        dq = None
+    dk = new(Lk) if dk is None else dk
+    dv = new(Lk) if dv is None else dv
+    for t in (dq, dk, dv):
+        if t is not None:
+            _bf16(t)
+            assert t.stride(2) == 1
+    if mask is not None:
+        mask = mask.float().contiguous()
+        assert mask.shape == (Nq, Lk)
+    if key_padding_mask is not None:
+        key_padding_mask = key_padding_mask.to(torch.uint8).contiguous()
+        assert key_padding_mask.shape == (B, Lk)
+    L.check(L.load().udt_mattn_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(mask), _ptr(key_padding_mask),
+                                   B, heads, D, Nq, Lk, q.stride(1), k.stride(1), v.stride(1), d_o.stride(1),
+                                   dq.stride(1) if dq is not None else 0, dk.stride(1), dv.stride(1), Lk,
+                                   q.stride(0), k.stride(0), v.stride(0), d_o.stride(0), dq.stride(0) if dq is not None else 0,
+                                   dk.stride(0), dv.stride(0), scale, _stream()), "udt_mattn_bwd")
+    return dq, dk, dv
+
+
+def gelu(a: torch.Tensor) -> torch.Tensor:
+    """exact-erf GELU of stored pre-activations a fp32 [rows, C] (a GEMM's fp32 output) -> bf16 [rows, C] (udt_gelu_fwd)"""
+    assert a.dtype == torch.float32 and a.is_contiguous() and a.dim() == 2
+    out = torch.empty(a.shape, dtype=torch.bfloat16, device=a.device)
+    L.check(L.load().udt_gelu_fwd(_ptr(a), _ptr(out), a.shape[0], a.shape[1], _stream()), "udt_gelu_fwd")
+    return out
+
+
+def gelu_bwd(a: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+    """dy bf16 [rows, C] -> d a bf16 [rows, C] on the stored fp32 pre-activations (udt_gelu_bwd)"""
+    _bf16(dy)
+    assert a.dtype == torch.float32 and a.is_contiguous() and a.dim() == 2 and dy.is_contiguous() and dy.shape == a.shape
+    da = torch.empty_like(dy)
+    L.check(L.load().udt_gelu_bwd(_ptr(a), _ptr(dy), _ptr(da), a.shape[0], a.shape[1], _stream()), "udt_gelu_bwd")
+    return da
+
+
+def ocr_ce(logits: torch.Tensor, targets: torch.Tensor, n_chars: torch.Tensor, weight: Optional[torch.Tensor] = None,
+           n_cls: Optional[int] = None):
+    """clamped character cross entropy and its seed (udt_ocr_ce_f32): logits fp32 [N, L, >= n_cls] (a row view: the last stride 1, the
+    position stride free), targets int32 [N, T], n_chars int32 [N] (1 <= n <= min(L, T): the CALLER validates on the host), weight fp32
+    [N] or None -> (loss fp32 [N], d_logits fp32 [N, L, n_cls])"""
+    assert logits.dtype == torch.float32 and logits.dim() == 3 and logits.stride(2) == 1
+    N, Lq = logits.shape[:2]
+    n_cls = logits.shape[2] if n_cls is None else int(n_cls)
+    if logits.stride(0) != Lq * logits.stride(1):                   # (a size-1 dimension carries any stride: give the kernel the dense form)
+        logits = logits.contiguous()
+    assert n_cls <= logits.shape[2]
+    assert targets.dtype == torch.int32 and targets.dim() == 2 and targets.shape[0] == N and targets.is_contiguous()
+    assert n_chars.dtype == torch.int32 and n_chars.shape == (N,) and n_chars.is_contiguous()
+    if weight is not None:
+        assert weight.dtype == torch.float32 and weight.shape == (N,) and weight.is_contiguous()
+    loss = torch.empty((N,), dtype=torch.float32, device=logits.device)
+    d_logits = torch.empty((N, Lq, n_cls), dtype=torch.float32, device=logits.device)
+    L.check(L.load().udt_ocr_ce_f32(_ptr(logits), _ptr(targets), _ptr(n_chars), _ptr(weight), _ptr(loss), _ptr(d_logits), N, Lq, n_cls,
+                                    logits.stride(1), targets.shape[1], n_cls, _stream()), "udt_ocr_ce_f32")
+    return loss, d_logits
+
+
 def local_loss_accumulate(probs: torch.Tensor, mask: torch.Tensor, seg_mask: torch.Tensor, gk9: torch.Tensor,
                           loss: torch.Tensor, heads: int, size: int) -> None:
     """loss [n] += per-layer local-loss term of n = probs.shape[0] / heads samples; sample i is scored against

@@ -49,6 +49,23 @@ class FullLoss(StandardDiffusionLoss):
         g = g / g.sum()
         return g.view(1, 1, kernel_size, kernel_size).tile(out_channels, 1, 1, 1)
 
+    def get_ocr_loss_decoded(self, decoded, r_bbox, label, weight=None, want_grad: bool = True):
+        """The part of ``get_ocr_loss`` (reference loss.py:178-190) AFTER ``first_stage_model.decode``: decoded fp32 [B, 3, H, W] on the
+        GPU (the decoder's output as it is, in [-1, 1]: the reference does not remap it), r_bbox: per image (top, bottom, left, right) on
+        the host, label: B strings -> ``self.predictor.calc_loss_boxes`` on the boxes (i, *r_bbox[i]): (ocr loss fp32 [B], its gradient
+        with respect to ``decoded`` fp32 [B, 3, H, W], or None without ``want_grad``).
+        The other half — ``model_output / scaler`` and the VAE decoder's backward-data pass, which carries this gradient to the UNet's
+        output — is not built: ``training.check_trainable`` still refuses ``ocr_enabled``.
+        ValueError when there is no predictor (``ocr_enabled`` was false at construction)."""
+        predictor = getattr(self, "predictor", None)
+        if predictor is None:
+            raise ValueError("get_ocr_loss_decoded needs the OCR predictor: construct FullLoss with ocr_enabled=True and a predictor_config")
+        if isinstance(r_bbox, torch.Tensor) and r_bbox.is_cuda:
+            raise ValueError("r_bbox is read on the host: pass it as a host tensor or a list")
+        rows = torch.as_tensor(r_bbox).reshape(-1, 4).tolist()
+        boxes = [[i] + list(bb) for i, bb in enumerate(rows)]
+        return predictor.calc_loss_boxes(decoded, boxes, label, weight=weight, want_grad=want_grad)
+
     def scores_map(self, hw) -> bool:
         """a t_attn layer is scored when min(h, w) >= min_attn_size: the reference's ``size >= min_attn_size`` for h == w (it
         raises for h != w), and never a blur over a map fewer than min_attn_size pixels high or wide"""

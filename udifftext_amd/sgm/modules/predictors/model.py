@@ -292,9 +292,11 @@ class PARSeq(nn.Module):
         return self.head(out.reshape(B * Lq, C), flags=H.GEMM_OUT_F32)[:, :len(self.tokenizer) - 2].reshape(B, Lq, -1)
 
     @torch.no_grad()
-    def forward(self, images, max_length: Optional[int] = None, memory=None):
+    def forward(self, images, max_length: Optional[int] = None, memory=None, refine_iters: Optional[int] = None):
         """images fp32 [N, 3, 32, 128] on the GPU -> fp32 logits [N, L, 95]; L <= max_label_length + 1 (the AR loop stops
-        once every sample has emitted EOS, system.py:122-124)"""
+        once every sample has emitted EOS, system.py:122-124).  refine_iters: run this many refinement passes instead of
+        ``self.refine_iters`` (the OCR loss runs all but the last here and the last one on a tape, ``refine_tape``)"""
+        n_refine = self.refine_iters if refine_iters is None else refine_iters
         dev = images.device
         testing = max_length is None
         max_length = self.max_label_length if max_length is None else min(max_length, self.max_label_length)
@@ -324,11 +326,11 @@ class PARSeq(nn.Module):
         else:
             tgt_in = torch.full((bs, 1), self.bos_id, dtype=torch.long, device=dev)
             logits = self.logits_of(self.decode(tgt_in, memory_kv, tgt_query=pos_queries))
-        if self.refine_iters:
+        if n_refine:
             query_mask = query_mask.clone()
             query_mask[torch.triu(torch.ones(num_steps, num_steps, dtype=torch.bool, device=dev), 2)] = 0
             bos = torch.full((bs, 1), self.bos_id, dtype=torch.long, device=dev)
-            for _ in range(self.refine_iters):
+            for _ in range(n_refine):
                 tgt_in = torch.cat([bos, logits[:, :-1].argmax(-1)], dim=1)
                 kpm = (tgt_in == self.eos_id).int().cumsum(-1) > 0
                 Lt = tgt_in.shape[1]
@@ -336,6 +338,20 @@ class PARSeq(nn.Module):
                                   tgt_query_mask=query_mask[:Lt, :Lt])
                 logits = self.logits_of(out)
         return logits
+
+    @torch.no_grad()
+    def refine_tape(self, images, tgt_in, memory_tape=None, tape: bool = True):
+        """Teacher-forced and reversible: the encoder and ONE refinement pass on given tokens tgt_in long [N, L] (BOS first; masks and
+        key padding as ``forward``'s refinement) -> (logits fp32 [N, L, 95], tape) with
+        ``tape.backward(d_logits fp32 [N, L, 95]) -> d_images fp32 [N, 3, 32, 128]`` (udifftext_amd.ocr_backward; weights frozen, dX
+        only).  memory_tape: ``ocr_backward.encoder_fwd(self.encoder, images)`` if the caller has already run it.
+        tape=False: the same launches and the same logits, nothing kept: returns (logits, None).
+        NotImplementedError unless refine_iters >= 1 and the decoder has one layer."""
+        from udifftext_amd import ocr_backward as OB
+        OB.check_supported(self)
+        memory, enc_bwd = OB.encoder_fwd(self.encoder, images, tape) if memory_tape is None else memory_tape
+        logits, dec_bwd = OB.refine_fwd(self, memory, tgt_in, tape)
+        return logits, (OB.RefineTape(enc_bwd, dec_bwd) if tape else None)
 
 
 class ParseqPredictor(nn.Module):
@@ -370,13 +386,11 @@ class ParseqPredictor(nn.Module):
 
     # ---- box-based entry points (pipeline.evaluate): the crops stay on the device as boxes of the sample batch, and all of them
     # are resampled in ONE launch (udt_crop_resize_aa_f32) instead of one F.interpolate per sliced crop as in ``transform``
-    def transform_boxes(self, samples, boxes):
-        """samples fp32 [B, 3, H, W] in [0, 1] on the GPU (what ``predict`` returns); boxes: a HOST int tensor or list [N, 5] =
-        (image index, top, bottom, left, right), half-open as samples[index, :, top:bottom, left:right] (test.py:81)
-        -> the normalised PARSeq input fp32 [N, 3, h, w] (hparams.img_size).  Boxes are validated here, on the host."""
-        from udifftext_amd import ops
+    @staticmethod
+    def _host_boxes(samples, boxes, what: str = "transform_boxes") -> torch.Tensor:
+        """the box table as a validated host int64 tensor [N, 5]; ValueError for device / non-integer tables and boxes outside the batch"""
         if isinstance(boxes, torch.Tensor) and boxes.is_cuda:
-            raise ValueError("transform_boxes takes boxes on the host (their values are validated before the launch)")
+            raise ValueError(f"{what} takes boxes on the host (their values are validated before the launch)")
         bx = torch.as_tensor(boxes).reshape(-1, 5)
         if bx.is_floating_point() or bx.dtype == torch.bool:
             raise ValueError(f"boxes must be integers, not {bx.dtype}")
@@ -385,6 +399,14 @@ class ParseqPredictor(nn.Module):
         for n, (i, t, b, l, r) in enumerate(bx.tolist()):
             if not (0 <= i < B and 0 <= t < b <= H and 0 <= l < r <= W):
                 raise ValueError(f"box {n} = (image {i}, rows {t}:{b}, columns {l}:{r}) does not lie in a batch of {B} images of {H} x {W}")
+        return bx
+
+    def transform_boxes(self, samples, boxes):
+        """samples fp32 [B, 3, H, W] in [0, 1] on the GPU (what ``predict`` returns); boxes: a HOST int tensor or list [N, 5] =
+        (image index, top, bottom, left, right), half-open as samples[index, :, top:bottom, left:right] (test.py:81)
+        -> the normalised PARSeq input fp32 [N, 3, h, w] (hparams.img_size).  Boxes are validated here, on the host."""
+        from udifftext_amd import ops
+        bx = self._host_boxes(samples, boxes)
         if bx.shape[0] == 0:
             return samples.new_empty((0, samples.shape[1]) + tuple(self.parseq.hparams.img_size), dtype=torch.float32)
         dev_boxes = bx.to(torch.int32).to(samples.device)
@@ -406,3 +428,70 @@ class ParseqPredictor(nn.Module):
             ce = F.cross_entropy(pred[:eos_id - 1].permute(1, 0)[None], gt_id[1:eos_id][None])
             losses.append(torch.clamp(ce, max=1.0)[None])
         return torch.cat(losses)
+
+    # ---- the OCR loss with its gradient (reference loss.py:178-190 under torch.autograd)
+    @torch.no_grad()
+    def calc_loss_boxes(self, samples, boxes, labels, weight=None, want_grad: bool = True):
+        """``calc_loss`` of the boxes of a decoded batch, and its gradient with respect to the batch.
+
+        samples fp32 [B, 3, H, W] on the GPU — handed to the scorer AS IT IS (the reference does not remap the decoder's [-1, 1]
+        output to [0, 1] before ``(x - 0.5) / 0.5``; kept); boxes: a HOST int table [N, 5] as ``transform_boxes`` takes it, with at
+        most one box per image when ``want_grad`` (loss.py:184); labels: N strings; weight: None (= 1), a number or fp32 [N] on the
+        device, the upstream cotangent of each row's loss.
+        -> (loss fp32 [N], d_samples fp32 [B, 3, H, W] or None): loss[n] = min(1, mean cross entropy over the label's characters,
+        EOS excluded), d_samples = sum_n weight[n] d loss[n] / d samples — zero for a clamped row (torch's clamp rule: the gradient
+        flows iff the unclamped value is <= 1), outside the boxes and for images without a box.
+
+        Steps: crop + resize + normalise (one launch), the autoregressive loop and all refinement passes but the last (no tape:
+        their logits reach the result through argmax only), the last pass on a tape, udt_ocr_ce_f32, the tape's reverse pass, the
+        crop-resize adjoint; without ``want_grad`` the same launches run and no activation is kept.  The tokens fed to the last pass are kept as ``self.parseq.last_refine_tokens``.  No host read apart
+        from the AR loop's early-exit check.
+        ValueError, on the host and BEFORE anything is launched: an empty label (NaN in the reference), a label longer than
+        max_label_length + 1 (no decoded length can hold it), a character outside the charset, len(labels) != N, no box, boxes ``transform_boxes`` refuses, a
+        repeated image index when ``want_grad``.  ValueError after the AR loop: a label longer than the decoded length L, which the
+        loop's early exit decides (a shape error in the reference).  NotImplementedError: refine_iters < 1 or dec_depth != 1."""
+        from udifftext_amd import ocr_backward as OB
+        from udifftext_amd import ops
+        pq = self.parseq
+        OB.check_supported(pq)
+        labels = list(labels)
+        for n, y in enumerate(labels):
+            if len(y) == 0:
+                raise ValueError(f"label {n} is empty: the mean over its characters is undefined")
+            if len(y) > pq.max_label_length + 1:
+                raise ValueError(f"label {n} has {len(y)} characters: more than the {pq.max_label_length + 1} positions PARSeq decodes")
+            unknown = sorted(set(y) - set(pq.tokenizer._stoi))
+            if unknown:
+                raise ValueError(f"label {n} has characters outside the scorer's charset: {unknown}")
+        bx = self._host_boxes(samples, boxes, "calc_loss_boxes")
+        if bx.shape[0] == 0 or bx.shape[0] != len(labels):
+            raise ValueError(f"{bx.shape[0]} boxes for {len(labels)} labels: the OCR loss takes one label per box, at least one")
+        if want_grad:
+            ops.unique_box_images(bx)
+        if not samples.is_cuda:
+            raise ValueError("calc_loss_boxes scores samples on the GPU (there is no CPU path)")
+        gt = pq.tokenizer.encode(labels)                               # host: [BOS] chars [EOS] [PAD]...
+        dev = samples.device
+        N = bx.shape[0]
+        if weight is not None and not isinstance(weight, torch.Tensor):
+            weight = torch.full((N,), float(weight), dtype=torch.float32)
+        if weight is not None:
+            weight = weight.to(device=dev, dtype=torch.float32).contiguous()
+        dev_boxes = bx.to(torch.int32).to(dev)
+        simg = samples.float().contiguous()
+        x = ops.crop_resize_aa(simg, dev_boxes, pq.hparams.img_size, mul=2.0, add=-1.0)
+        memory_tape = OB.encoder_fwd(pq.encoder, x, want_grad)       # (want_grad False: the same launches, nothing kept)
+        logits = pq(x, memory=memory_tape[0], refine_iters=pq.refine_iters - 1)
+        L = logits.shape[1]
+        longest = max(len(y) for y in labels)
+        if longest > L:
+            raise ValueError(f"a label has {longest} characters but the decoded length is {L} (every row emitted EOS by then)")
+        tgt_in = torch.cat([torch.full((N, 1), pq.bos_id, dtype=torch.long, device=dev), logits[:, :-1].argmax(-1)], dim=1)
+        pq.last_refine_tokens = tgt_in
+        logits, tape = pq.refine_tape(x, tgt_in, memory_tape=memory_tape, tape=want_grad)
+        targets = gt[:, 1:].to(torch.int32).contiguous().to(dev)
+        n_chars = torch.tensor([len(y) for y in labels], dtype=torch.int32).to(dev)
+        loss, d_logits = ops.ocr_ce(logits, targets, n_chars, weight)
+        if not want_grad:
+            return loss, None
+        return loss, ops.crop_resize_aa_bwd(tape.backward(d_logits), dev_boxes, simg.shape, mul=2.0)
