@@ -1,6 +1,7 @@
 """The row-wise attend-and-excite loop on the MI355X: udt_aae_row_update_f32 against the restated rule (tests/aae_rows_ref.py) and the real
 reference's B = 1 loop (tests/golden/aae_rows_golden.npz), EulerEDMSampler.attend_and_excite_rows against attend_and_excite at B = 1 and
-against the written-out row-wise loop at B = 2, independence of a row from its batch mate, the sampler's schedule
+against the written-out row-wise loop at B = 2, independence of a row from its batch mate, attend_and_excite at B = 2 against its
+restated rule, results that alias neither the runner's static latent nor the caller's x, the sampler's schedule
 (sample_rows_with_attend_and_excite) and pipeline.predict_many with cfgs.aae_enabled end to end.
 
 Reference: sgm/modules/diffusionmodules/sampling.py:233-252,355-420.
@@ -338,6 +339,75 @@ def test_a_row_owes_nothing_to_its_batch_mate(engine, env, pair):
             d = float((xa[keep] - xb[keep]).abs().max())
             print(f"graph {graph}: row {keep} with row {swap} replaced: counts {ia} -> {ib}, max |d x[{keep}]| {d:.3e}")
             assert torch.equal(xa[keep], xb[keep]), (graph, keep, d)
+
+
+# ------------------------------------------------------------------------------------------------ the joint loop at B = 2
+@pytest.fixture(scope="module")
+def joint(engine, env, g15):
+    """the G13 sample stacked with a second row: the same conditioning and masks, 0.5 * x; the eager batched evaluation and the two
+    rows' losses at the start"""
+    x0, sigma, alpha, c, batch = _aae_point(env, g15)
+    two = lambda v: v.repeat((2,) + (1,) * (v.dim() - 1))
+    x = torch.cat([x0, 0.5 * x0])
+    s2, c2, b2 = sigma.reshape(1).repeat(2), {k: two(v) for k, v in c.items()}, {k: two(v) for k, v in batch.items()}
+    sampler = env.pipeline.init_sampling(10, 5.0, env.dev)
+    c_noise = sampler.get_c_noise(x, engine, s2).float()
+    unet = engine.model.diffusion_model
+    ev = lambda xx: env.bw.unet_local_loss_grad(unet, engine.loss_fn, xx, c_noise, c2["concat"], c2["t_crossattn"], b2["mask"], b2["seg_mask"])
+
+    class P:
+        pass
+    P.x, P.s2, P.c2, P.b2, P.alpha, P.ev, P.loss0 = x, s2, c2, b2, alpha, ev, [float(v) for v in ev(x)[0]]
+    return P
+
+
+def test_joint_loop_equals_its_restated_rule_at_batch_2(engine, env, joint):
+    """attend_and_excite at B = 2 against its rule written out on public pieces (backward.unet_local_loss_grad, ops.axpy_, the stop
+    rule ``not iter_enabled or (loss <= thres).all() or iters > max_iter`` over all rows jointly): bit-equal latents and the same
+    number added to aae_evaluations, through the captured runner (the loop runs on its static latent) and through eager launches.
+    thres +1e9: one update; -1e9: to the cap, max_iter + 1 updates; the mean of the two rows' first losses: whatever the rule gives
+    (printed)."""
+    P, max_iter = joint, 3
+    samplers = {graph: env.pipeline.init_sampling(10, 5.0, env.dev) for graph in (True, False)}
+    for name, thres in (("+1e9", 1e9), ("-1e9", -1e9), ("mean of the first losses", 0.5 * (P.loss0[0] + P.loss0[1]))):
+        x, iters = P.x.clone(), 0
+        while True:
+            loss, grad = P.ev(x)
+            env.ops.axpy_(x, grad, -P.alpha)
+            iters += 1
+            if bool((loss <= thres).all()) or iters > max_iter:
+                break
+        print(f"thres {name} ({thres:.6g}; first losses {P.loss0}): the restated rule takes {iters} updates")
+        if name != "mean of the first losses":
+            assert iters == (1 if thres > 0 else max_iter + 1), (name, iters)
+        for graph, sampler in samplers.items():
+            n0 = getattr(sampler, "aae_evaluations", 0)
+            with _graph_mode(graph):
+                got = sampler.attend_and_excite(P.x, engine, P.s2, P.c2, P.b2, P.alpha, True, thres, max_iter=max_iter)
+            assert (getattr(sampler, "_aae_runner", None) is not None) == graph
+            assert sampler.aae_evaluations - n0 == iters, (name, graph, sampler.aae_evaluations - n0, iters)
+            assert torch.equal(got.view(I32), x.view(I32)), (name, graph, float((got - x).abs().max()))
+
+
+def test_update_results_alias_neither_the_runner_nor_the_input(engine, env, joint):
+    """both update functions through the captured runner: a result keeps its bits when the next call reloads and updates the runner's
+    static latent, the callers' x are not written, and no result shares storage with the static buffer"""
+    P = joint
+    sampler = env.pipeline.init_sampling(10, 5.0, env.dev)
+    updates = {"attend_and_excite": sampler.attend_and_excite, "attend_and_excite_rows": lambda *a, **k: sampler.attend_and_excite_rows(*a, **k)[0]}
+    for name, update in updates.items():
+        x_a, x_b = P.x.clone(), (0.75 * P.x).contiguous()
+        a0, b0 = x_a.clone(), x_b.clone()
+        r_a = update(x_a, engine, P.s2, P.c2, P.b2, P.alpha, True, -1e9, max_iter=1)          # (two updates of every row)
+        bits = r_a.clone()
+        r_b = update(x_b, engine, P.s2, P.c2, P.b2, P.alpha, True, -1e9, max_iter=1)
+        static = sampler._aae_runner.x
+        assert torch.equal(r_a.view(I32), bits.view(I32)), (name, "the first result changed with the second call")
+        assert not torch.equal(r_a, r_b) and not torch.equal(r_a, a0), (name, "precondition: the calls update, and differ")
+        assert torch.equal(x_a.view(I32), a0.view(I32)) and torch.equal(x_b.view(I32), b0.view(I32)), (name, "a caller's x was written")
+        ptrs = [t.untyped_storage().data_ptr() for t in (static, r_a, r_b, x_a, x_b)]
+        assert len(set(ptrs)) == len(ptrs), (name, "shared storage", ptrs)
+        assert torch.equal(static.view(I32), r_b.view(I32))                  # (the static latent is where the last call left it)
 
 
 # ------------------------------------------------------------------------------------------------ the sampler and predict_many

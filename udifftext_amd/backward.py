@@ -483,15 +483,11 @@ class GraphedLocalLossGrad:
         self.graph = g
 
     def __call__(self, x, timesteps, concat, t_context, mask, seg_mask):
-        for dst, src in zip(self.inputs, (x, timesteps, concat, t_context, mask, seg_mask)):
-            dst.copy_(src)
-        if self.graph is None:
-            self._capture()
-        self.graph.replay()
-        return self.loss, self.grad
+        self.load(x, timesteps, concat, t_context, mask, seg_mask)
+        return self.replay()
 
-    # the row-wise attend-and-excite loop (EulerEDMSampler.attend_and_excite_rows) keeps its latent IN the static buffer: the inputs
-    # are copied once per update step, every iteration is one replay and one in-place update of ``x``
+    # the attend-and-excite loops (EulerEDMSampler.attend_and_excite, attend_and_excite_rows) keep their latent IN the static buffer:
+    # the inputs are copied once per update step, every iteration is one replay and one in-place update of ``x``
     @property
     def x(self) -> torch.Tensor:
         """the static latent the graph reads (fp32, the shape it was built for)"""

@@ -161,45 +161,53 @@ def _lane_streams(device: torch.device, n: int):
     return _LANE_STREAMS[key]
 
 
+def _form_batch(cfgs, model, sampler, batches, image_seeds, idx, device, masks=False):
+    """one sampling batch from the input batches ``idx`` of a unit: per input batch — in the order and from the generator that
+    ``predict`` batch by batch would use, inside rng.per_image when ``image_seeds`` are given — conditioning,
+    get_init_noise and, right after it, the run's step noise (ancestral / churned samplers); then the one-image-size check and the
+    concatenation.  -> (x, cond, uc, fb, kw, sizes, parts): fb is None, or with ``masks`` the dict of ``mask`` / ``seg_mask``
+    concatenated over the unit (attend-and-excite reads them); kw holds ``noise`` [steps, fused batch, 4, h, w] where the sampler
+    draws any; sizes are the images per input batch, parts the per-batch tensors (a lane keeps them alive)."""
+    draw_noise = getattr(sampler, "draw_step_noise", None)
+    xs, cs, ucs, noises, bs = [], [], [], [], []
+    for gi in idx:
+        b, buc = prepare_batch(batches[gi], device)
+        seeds = image_seeds[gi] if image_seeds is not None else None
+        with (rng.per_image(seeds) if seeds is not None else contextlib.nullcontext()):
+            c, uc = model.conditioner.get_unconditional_conditioning(
+                b, batch_uc=buc, force_uc_zero_embeddings=cfgs.force_uc_zero_embeddings)
+            xs.append(sampler.get_init_noise(cfgs, model, cond=c, batch=b, uc=uc))
+            if draw_noise is not None:
+                noises.append(draw_noise(xs[-1].shape, xs[-1].device, None, cfgs.init_step))
+        cs.append(c)
+        ucs.append(uc)
+        bs.append(b)
+    if any(x.shape[1:] != xs[0].shape[1:] for x in xs):
+        raise ValueError("batches fused into one sampling batch need one image size (use fuse=1)")
+    cat = lambda ts, dim=0: torch.cat(ts, dim) if len(ts) > 1 else ts[0]
+    cat_cond = lambda ds: _cat_cond(ds) if len(ds) > 1 else ds[0]
+    kw = {"noise": cat(noises, 1)} if noises and noises[0] is not None else {}
+    fb = {k: cat([b[k] for b in bs]) for k in ("mask", "seg_mask")} if masks else None
+    return cat(xs), cat_cond(cs), cat_cond(ucs), fb, kw, [x.shape[0] for x in xs], (xs, cs, ucs, noises)
+
+
+def _split(img, z, sizes):
+    """the fused batch's outputs back per input batch"""
+    bounds = [sum(sizes[:k]) for k in range(len(sizes) + 1)]
+    return [(img[a:b], z[a:b]) for a, b in zip(bounds, bounds[1:])]
+
+
 def _predict_many_aae(cfgs, model, sampler, sample_rows, batches, units, device, image_seeds, record_losses):
     """the attend-and-excite branch of ``predict_many``: sampling batch after sampling batch on the current stream (see there)"""
     from udifftext_amd import ops
-    gpu = torch.device(device).type == "cuda"
-    draw_noise = getattr(sampler, "draw_step_noise", None)
     out = []
     for idx in units:
-        xs, cs, ucs, sizes, noises, masks, segs = [], [], [], [], [], [], []
         with ops.launch_context(cu_share=1):
-            for gi in idx:
-                b, buc = prepare_batch(batches[gi], device)
-                seeds = image_seeds[gi] if image_seeds is not None else None
-                with (rng.per_image(seeds) if seeds is not None else contextlib.nullcontext()):
-                    c, uc = model.conditioner.get_unconditional_conditioning(
-                        b, batch_uc=buc, force_uc_zero_embeddings=cfgs.force_uc_zero_embeddings)
-                    xs.append(sampler.get_init_noise(cfgs, model, cond=c, batch=b, uc=uc))
-                    if draw_noise is not None:      # churned steps: the run's step noise, right after the initial noise
-                        noises.append(draw_noise(xs[-1].shape, xs[-1].device, None, cfgs.init_step))
-                cs.append(c)
-                ucs.append(uc)
-                sizes.append(xs[-1].shape[0])
-                masks.append(b["mask"])
-                segs.append(b["seg_mask"])
-            if any(x.shape[1:] != xs[0].shape[1:] for x in xs):
-                raise ValueError("batches fused into one sampling batch need one image size (use fuse=1)")
-            fx = torch.cat(xs, 0) if len(xs) > 1 else xs[0]
-            fc = _cat_cond(cs) if len(cs) > 1 else cs[0]
-            fuc = _cat_cond(ucs) if len(ucs) > 1 else ucs[0]
-            fb = {"mask": torch.cat(masks, 0) if len(masks) > 1 else masks[0], "seg_mask": torch.cat(segs, 0) if len(segs) > 1 else segs[0]}
-            kw = {}
-            if noises and noises[0] is not None:
-                kw["noise"] = torch.cat(noises, 1) if len(noises) > 1 else noises[0]      # [steps, fused batch, 4, h, w]
+            fx, fc, fuc, fb, kw, sizes, _ = _form_batch(cfgs, model, sampler, batches, image_seeds, idx, device, masks=True)
             z = sample_rows(model, fx, fc, fb, fuc, init_step=cfgs.init_step, record_losses=record_losses, **kw)
             img = torch.clamp((model.decode_first_stage(z) + 1.0) / 2.0, min=0.0, max=1.0)
-        o = 0
-        for nb in sizes:
-            out.append((img[o:o + nb], z[o:o + nb]))
-            o += nb
-    if gpu:
+        out.extend(_split(img, z, sizes))
+    if torch.device(device).type == "cuda":
         ops.check_async_errors()
     return out
 
@@ -250,7 +258,6 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
     # lanes in lock-stepped groups with a cross-lane join before and after every sampling loop: ~35 ms of each 1.28 s group
     # had no sampling running, and a slow lane held the others.)
     lane_sampler = getattr(sampler, "sample_lane", None)
-    draw_noise = getattr(sampler, "draw_step_noise", None)
     if auto:
         # automatic fusing joins consecutive batches only while their image size is equal (one size per sampling batch, as the
         # reference's target_size_as_tuple[0]): a list of mixed sizes works; an explicit fuse > 1 over mixed sizes raises below
@@ -272,39 +279,16 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
         after(lane, main)
     for u, idx in enumerate(units):
         lane = lanes[u % n_used]
-        xs, cs, ucs, sizes, noises = [], [], [], [], []
         with on(lane), ops.launch_context(cu_share=n_used):
-            for gi in idx:
-                b, buc = prepare_batch(batches[gi], device)
-                seeds = image_seeds[gi] if image_seeds is not None else None
-                with (rng.per_image(seeds) if seeds is not None else contextlib.nullcontext()):
-                    c, uc = model.conditioner.get_unconditional_conditioning(
-                        b, batch_uc=buc, force_uc_zero_embeddings=cfgs.force_uc_zero_embeddings)
-                    xs.append(sampler.get_init_noise(cfgs, model, cond=c, batch=b, uc=uc))
-                    if draw_noise is not None:      # ancestral / churned samplers: the run's step noise, right after the initial noise
-                        noises.append(draw_noise(xs[-1].shape, xs[-1].device, None, cfgs.init_step))
-                cs.append(c)
-                ucs.append(uc)
-                sizes.append(xs[-1].shape[0])
-            if any(x.shape[1:] != xs[0].shape[1:] for x in xs):
-                raise ValueError("batches fused into one sampling batch need one image size (use fuse=1)")
-            fx = torch.cat(xs, 0) if len(xs) > 1 else xs[0]
-            fc = _cat_cond(cs) if len(cs) > 1 else cs[0]
-            fuc = _cat_cond(ucs) if len(ucs) > 1 else ucs[0]
-            kw = {}
-            if noises and noises[0] is not None:
-                kw["noise"] = torch.cat(noises, 1) if len(noises) > 1 else noises[0]      # [steps, fused batch, 4, h, w]
+            fx, fc, fuc, _, kw, sizes, parts = _form_batch(cfgs, model, sampler, batches, image_seeds, idx, device)
             if lane_sampler is not None:
                 z = lane_sampler(model, fx, fc, fuc, slot=u % n_used, n_lanes=n_used, init_step=cfgs.init_step, deferred_checks=checks,
                                  **kw)
             else:       # (stub samplers of the CPU tests: the group interface, one batch at a time)
                 z = sampler.sample_in_flight(model, [fx], [fc], [fuc], init_step=cfgs.init_step, deferred_checks=checks)[0]
             img = torch.clamp((model.decode_first_stage(z) + 1.0) / 2.0, min=0.0, max=1.0)
-        keep.append((xs, cs, ucs, fx, fc, fuc, z, noises))     # tensors of a lane stream: alive until the final synchronisation
-        o = 0
-        for nb in sizes:
-            out.append((img[o:o + nb], z[o:o + nb]))
-            o += nb
+        keep.append((parts, fx, fc, fuc, z))                   # tensors of a lane stream: alive until the final synchronisation
+        out.extend(_split(img, z, sizes))
     for lane in lanes:
         after(main, lane)
     for chk in checks:

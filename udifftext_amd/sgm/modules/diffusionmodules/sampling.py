@@ -10,8 +10,9 @@ c_in, c_out) are computed on the host from the fp32 tables — no ``.item()`` sy
   udt_unet_input (x*c_in into the NHWC bf16 CFG pair) -> UNet kernels -> udt_cfg_euler_step (c_out, CFG, Euler),
 with the step-invariant pieces hoisted out of the loop (text k|v projections of all 16 transformers, the
 concat channels of the UNet input).  Attention maps are only emitted where they are consumed (noise search).
-The heavier side paths (attend-and-excite: needs autograd through the UNet; attention-map plots / GIFs) are
-out of scope and raise.
+The side paths of EulerEDMSampler — attend-and-excite (``_sample_with_attend_and_excite``, and row by row for
+pipeline.predict_many ``sample_rows_with_attend_and_excite``: one schedule, ``_aae_steps``) and the ``detailed``
+attention-map dump — run eager steps around the written-out reverse pass (udifftext_amd.backward).
 
 Every sampler describes step i as a plan of UNet evaluations, each ending in ONE fused launch: ``EulerEval``
 (udt_cfg_euler_step, the step above: EulerEDMSampler), ``Eval`` (udt_cfg_sampler_step: HeunEDMSampler, EulerAncestralSampler,
@@ -878,55 +879,16 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         sigma = model.denoiser.possibly_quantize_sigma(sigma).reshape(-1)
         return model.denoiser.possibly_quantize_c_noise(model.denoiser.scaling(sigma)[3])
 
-    def attend_and_excite(self, x, model, sigma, cond, batch, alpha, iter_enabled, thres, max_iter=20):
-        """reference sampling.py:233-252: x <- x - alpha * d local_loss / d x, once, or (iter_enabled) until the loss falls to
-        ``thres`` or max_iter is passed.  The network sees the RAW x (no c_in scaling — the reference calls model.model directly)
-        and only the conditional batch; the gradient runs through the HIP path's written-out reverse pass
-        (udifftext_amd.backward.unet_local_loss_grad) — per sample, where the reference only accepts B = 1."""
-        from udifftext_amd import backward
-        require_gpu(x, "EulerEDMSampler.attend_and_excite")
-        c_noise = self.get_c_noise(x, model, sigma)
-        unet = model.model.diffusion_model
-        x = x.detach().clone().float().contiguous()
-        args = (c_noise.float(), cond["concat"], cond["t_crossattn"], batch["mask"], batch["seg_mask"])
-        evaluate = lambda xx: backward.unet_local_loss_grad(unet, model.loss_fn, xx, *args)
-        if self.use_graphs and AAE_GRAPH:
-            # the evaluation's launch sequence depends on the shapes only: captured once per sampler, replayed for every update of
-            # every step (the timestep index, latent and conditioning are device data in static buffers)
-            runner = getattr(self, "_aae_runner", None)
-            key = denoiser_key(model.denoiser)                             # (a swapped denoiser gets a capture of its own)
-            if runner is None or not runner.valid_for(unet, x, *args) or getattr(self, "_aae_key", None) != key:
-                runner = self._aae_runner = None                           # (drop the old pool before the new capture)
-                try:
-                    runner = backward.GraphedLocalLossGrad(unet, model.loss_fn, x, *args)
-                    runner(x, *args)
-                    self._aae_runner, self._aae_key = runner, key
-                except Exception as e:
-                    if not _is_capture_failure(e):
-                        raise
-                    print(f"[udifftext_amd] attend-and-excite: hipGraph capture unavailable ({type(e).__name__}: {e}); eager launches")
-                    runner = None
-            if runner is not None:
-                evaluate = lambda xx: runner(xx, *args)
-        iters = 0
-        while True:
-            loss, grad = evaluate(x)
-            ops.axpy_(x, grad, -float(alpha))
-            iters += 1
-            if not iter_enabled or bool((loss <= thres).all()) or iters > max_iter:
-                break
-        self.aae_evaluations = getattr(self, "aae_evaluations", 0) + iters     # (how many gradients a sampling run took)
-        return x
-
-    # ------------------------------------------------------------------------- attend-and-excite, row by row
-    def _aae_rows_runner(self, model, unet, x, args):
-        """the captured evaluation ``attend_and_excite`` uses (one cache, one invalidation rule: shapes, weights, denoiser) with the
-        inputs loaded into its static buffers; None -> eager launches (graphs off, or capture unavailable)"""
+    def _aae_runner_for(self, model, unet, x, args):
+        """the captured evaluation of both update loops (one cache, one invalidation rule: shapes, weights, denoiser) with the inputs
+        loaded into its static buffers; None -> eager launches (graphs off, or capture unavailable).  The evaluation's launch
+        sequence depends on the shapes only: captured once per sampler, replayed for every update of every step (the timestep index,
+        latent and conditioning are device data in static buffers)"""
         from udifftext_amd import backward
         if not (self.use_graphs and AAE_GRAPH):
             return None
         runner = getattr(self, "_aae_runner", None)
-        key = denoiser_key(model.denoiser)
+        key = denoiser_key(model.denoiser)                                 # (a swapped denoiser gets a capture of its own)
         if runner is None or not runner.valid_for(unet, x, *args) or getattr(self, "_aae_key", None) != key:
             runner = self._aae_runner = None                               # (drop the old pool before the new capture)
             try:
@@ -942,6 +904,37 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
             runner.load(x, *args)
         return runner
 
+    def _aae_begin(self, x, model, sigma, cond, batch, who):
+        """what both update loops start from -> (xs, evaluate, runner): xs the fp32 latent the loop updates in place — the runner's
+        static buffer, or a private clone of ``x`` under eager launches (runner None) — and evaluate() -> (loss, grad) at xs"""
+        from udifftext_amd import backward
+        require_gpu(x, who)
+        c_noise = self.get_c_noise(x, model, sigma)
+        unet = model.model.diffusion_model
+        x = x.detach().clone().float().contiguous()
+        args = (c_noise.float(), cond["concat"], cond["t_crossattn"], batch["mask"], batch["seg_mask"])
+        runner = self._aae_runner_for(model, unet, x, args)
+        if runner is not None:
+            return runner.x, runner.replay, runner
+        return x, lambda: backward.unet_local_loss_grad(unet, model.loss_fn, x, *args), None
+
+    def attend_and_excite(self, x, model, sigma, cond, batch, alpha, iter_enabled, thres, max_iter=20):
+        """reference sampling.py:233-252: x <- x - alpha * d local_loss / d x, once, or (iter_enabled) until the loss falls to
+        ``thres`` or max_iter is passed.  The network sees the RAW x (no c_in scaling — the reference calls model.model directly)
+        and only the conditional batch; the gradient runs through the HIP path's written-out reverse pass
+        (udifftext_amd.backward.unet_local_loss_grad) — per sample, where the reference only accepts B = 1.  With a captured
+        runner one iteration is one graph replay on the runner's static latent and one axpy that updates it in place."""
+        xs, evaluate, runner = self._aae_begin(x, model, sigma, cond, batch, "EulerEDMSampler.attend_and_excite")
+        iters = 0
+        while True:
+            loss, grad = evaluate()
+            ops.axpy_(xs, grad, -float(alpha))
+            iters += 1
+            if not iter_enabled or bool((loss <= thres).all()) or iters > max_iter:
+                break
+        self.aae_evaluations = getattr(self, "aae_evaluations", 0) + iters     # (how many gradients a sampling run took)
+        return xs.clone() if runner is not None else xs
+
     def attend_and_excite_rows(self, x, model, sigma, cond, batch, alpha, iter_enabled, thres, max_iter=20):
         """``attend_and_excite`` with every row of the batch on its OWN B = 1 loop (reference sampling.py:240-252 compares a
         one-element loss): a row whose loss has fallen to ``thres``, or that has passed max_iter, is frozen — it takes no further
@@ -951,23 +944,13 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         launch that updates it in place, and — only with iter_enabled — the read-back of one int32 (the number of active rows);
         without iter_enabled there is exactly one evaluation and no host synchronisation.
         -> (x, iters): iters int32 [B] on the device, the updates each row took.  At B = 1: ``attend_and_excite``, bit for bit."""
-        from udifftext_amd import backward
-        require_gpu(x, "EulerEDMSampler.attend_and_excite_rows")
-        c_noise = self.get_c_noise(x, model, sigma)
-        unet = model.model.diffusion_model
-        x = x.detach().clone().float().contiguous()
-        args = (c_noise.float(), cond["concat"], cond["t_crossattn"], batch["mask"], batch["seg_mask"])
-        B = x.shape[0]
-        runner = self._aae_rows_runner(model, unet, x, args)
-        if runner is not None:
-            xs, evaluate = runner.x, runner.replay
-        else:
-            xs, evaluate = x, lambda: backward.unet_local_loss_grad(unet, model.loss_fn, x, *args)
+        xs, evaluate, runner = self._aae_begin(x, model, sigma, cond, batch, "EulerEDMSampler.attend_and_excite_rows")
+        B = xs.shape[0]
         st = getattr(self, "_aae_rows_state", None)
-        if st is None or st[0].shape[1] != B or st[0].device != x.device:
-            st = self._aae_rows_state = (torch.empty((2, B), dtype=torch.int32, device=x.device),
-                                         torch.empty((2, B), dtype=torch.int32, device=x.device),
-                                         torch.empty((1,), dtype=torch.int32, device=x.device))
+        if st is None or st[0].shape[1] != B or st[0].device != xs.device:
+            st = self._aae_rows_state = (torch.empty((2, B), dtype=torch.int32, device=xs.device),
+                                         torch.empty((2, B), dtype=torch.int32, device=xs.device),
+                                         torch.empty((1,), dtype=torch.int32, device=xs.device))
         s_in, s_out, n_act = st
         s_in[0].fill_(1)
         s_in[1].zero_()
@@ -994,35 +977,26 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         self.aae_frozen_row_evaluations = getattr(self, "aae_frozen_row_evaluations", 0) + frozen
         return (xs.clone() if runner is not None else xs), iters
 
-    def sample_rows_with_attend_and_excite(self, model, x, cond, batch, uc, num_steps=None, init_step=0,
-                                           noise: Optional[torch.Tensor] = None, record_losses: bool = True):
-        """the attend-and-excite sampling loop for a batch of independent images (pipeline.predict_many): the schedule of
-        ``_sample_with_attend_and_excite`` — alpha = 20 sqrt(scale_i), iterated at steps 5, 9, ..., 25 down to thresholds
-        -0.5 ... -0.8, a churned step's noise added before the update, update and step at sigma_hat — with the update taken row by
-        row (``attend_and_excite_rows``), and without the per-step VAE decode, the GIF and the prints.  record_losses: every step
-        emits its attention maps and the per-row local loss goes into a device [steps, B] tensor, copied to ``last_row_losses``
-        once at the end; without it the steps are the fast steps (the latent then differs by the two text-attention forms'
-        rounding)."""
-        import numpy as np
-        self._check_fast_path(model)
-        require_gpu(x, "EulerEDMSampler.sample_rows_with_attend_and_excite")
-        uc = default(uc, cond)
-        if noise is None:
-            noise = self.draw_step_noise(x.shape, x.device, num_steps, init_step)
+    # --------------------------------------------------------------------- the sampling loops around the updates
+    def _begin_loop(self, model, x, cond, uc, num_steps):
+        """-> (sig, x, stepper): the host sigma schedule, x as fp32 scaled by sqrt(1 + sigma_0^2) (in place where x already is
+        contiguous fp32, like the reference :54), and the stepper of this batch"""
         sig = self._host_sigmas(num_steps)
-        num_sigmas = len(sig)
         x = x.float().contiguous()
         x *= (1.0 + sig[0] ** 2.0) ** 0.5
-        scales = np.linspace(start=1.0, stop=0, num=num_sigmas)
+        return sig, x, _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self._scale, pair=self._pair)
+
+    def _aae_steps(self, update, model, x, cond, batch, sig, init_step, noise):
+        """the attend-and-excite schedule (reference sampling.py:355-386): before denoising step i the latent takes ``update`` with
+        alpha = 20 sqrt(scale_i), iterated at steps 5, 9, ..., 25 down to thresholds -0.5 ... -0.8.  A churned step adds its noise
+        BEFORE the update, and the update and the step run at sigma_hat (reference :328-336).  Yields (i, e, x) — the step's index,
+        its EulerEval and the updated latent — for the caller to step IN PLACE."""
+        scales = np.linspace(start=1.0, stop=0, num=len(sig))
         iter_lst = np.linspace(start=5, stop=25, num=6, dtype=np.int32)
         thres_lst = np.linspace(start=-0.5, stop=-0.8, num=6)
-        B = x.shape[0]
-        stepper = _Stepper(model, cond, uc, B, x.shape[2:], self._scale, pair=self._pair)
-        s_in = x.new_ones([B])
-        steps = list(self.get_sigma_gen(num_sigmas, init_step=init_step))
-        losses = torch.zeros((len(steps), B), dtype=torch.float32, device=x.device) if record_losses else None
+        s_in = x.new_ones([x.shape[0]])
         slot = 0                                                           # the k-th churned step reads draw k
-        for k, i in enumerate(steps):
+        for i in self.get_sigma_gen(len(sig), init_step=init_step):
             (e,) = self.step_plan(sig, i, init_step)
             alpha = 20 * np.sqrt(scales[i])
             iter_enabled = i in iter_lst
@@ -1030,7 +1004,26 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
             if e.churn != 0.0:
                 ops.axpy_(x, noise[slot], e.churn)
                 slot += 1
-            x, _ = self.attend_and_excite_rows(x, model, s_in * e.sigma, cond, batch, alpha, iter_enabled, thres)
+            x = update(x, model, s_in * e.sigma, cond, batch, alpha, iter_enabled, thres)
+            yield i, e, x
+
+    def sample_rows_with_attend_and_excite(self, model, x, cond, batch, uc, num_steps=None, init_step=0,
+                                           noise: Optional[torch.Tensor] = None, record_losses: bool = True):
+        """the attend-and-excite sampling loop for a batch of independent images (pipeline.predict_many): the schedule of
+        ``_aae_steps`` with the update taken row by row (``attend_and_excite_rows``), and without the per-step VAE decode, the GIF
+        and the prints of ``_sample_with_attend_and_excite``.  record_losses: every step emits its attention maps and the per-row
+        local loss goes into a device [steps, B] tensor, copied to ``last_row_losses`` once at the end; without it the steps are
+        the fast steps (the latent then differs by the two text-attention forms' rounding)."""
+        self._check_fast_path(model)
+        require_gpu(x, "EulerEDMSampler.sample_rows_with_attend_and_excite")
+        uc = default(uc, cond)
+        if noise is None:
+            noise = self.draw_step_noise(x.shape, x.device, num_steps, init_step)
+        sig, x, stepper = self._begin_loop(model, x, cond, uc, num_steps)
+        n = max(0, len(sig) - 1 - init_step)
+        losses = torch.zeros((n, x.shape[0]), dtype=torch.float32, device=x.device) if record_losses else None
+        rows = lambda *a: self.attend_and_excite_rows(*a)[0]
+        for k, (i, e, x) in enumerate(self._aae_steps(rows, model, x, cond, batch, sig, init_step, noise)):
             stepper.step(x, e.sigma, e.sigma_next, emit_maps=record_losses)
             if record_losses:
                 losses[k].copy_(model.loss_fn.get_min_local_loss(stepper.unet.attn_map_cache, batch["mask"], batch["seg_mask"],
@@ -1104,11 +1097,8 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         # and the label's per-character maps saved.  That one step runs with map emission (eager launches, the xattn chain); every
         # other step is the fast step — the loop is the same Euler loop, so the latent equals the plain call's up to the two
         # text-attention forms' rounding
-        sig = self._host_sigmas(num_steps)
-        x = x.float().contiguous()
-        x *= (1.0 + sig[0] ** 2.0) ** 0.5                                  # in place, like the reference :54
+        sig, x, stepper = self._begin_loop(model, x, cond, uc, num_steps)
         name = name if name is not None else (batch["name"][0] if batch is not None and "name" in batch else "sample")
-        stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self._scale, pair=self._pair)
         mid = (len(sig) - 1) // 2
         slot = 0                                                           # the k-th churned step reads draw k
         for i in self.get_sigma_gen(len(sig), init_step=init_step):
@@ -1123,35 +1113,15 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
 
     def _sample_with_attend_and_excite(self, model, x, cond, batch, uc, num_steps, init_step, name, detailed, noise=None):
         """reference sampling.py:355-420 with aae_enabled: before every denoising step the latent takes attend-and-excite updates
-        (alpha = 20 sqrt(scale_i); iterated at steps 5, 9, ..., 25 down to thresholds -0.5 ... -0.8), the local loss of every step
-        is collected and every intermediate denoised latent decoded (the reference writes them as a GIF; imageio is optional
-        here).  Eager launches: the update's step count is data-dependent.  A churned step adds its noise BEFORE the update, and
-        the update and the step run at sigma_hat (reference :328-336)."""
-        import numpy as np
-        sig = self._host_sigmas(num_steps)
-        num_sigmas = len(sig)
-        x = x.float().contiguous()
-        x *= (1.0 + sig[0] ** 2.0) ** 0.5
+        (the schedule of ``_aae_steps``, the joint update ``attend_and_excite``), the local loss of every step is collected and
+        every intermediate denoised latent decoded (the reference writes them as a GIF; imageio is optional here).  Eager
+        launches: the update's step count is data-dependent."""
+        sig, x, stepper = self._begin_loop(model, x, cond, uc, num_steps)
         name = name if name is not None else (batch["name"][0] if batch is not None and "name" in batch else "sample")
-        scales = np.linspace(start=1.0, stop=0, num=num_sigmas)
-        iter_lst = np.linspace(start=5, stop=25, num=6, dtype=np.int32)
-        thres_lst = np.linspace(start=-0.5, stop=-0.8, num=6)
-        B = x.shape[0]
-        stepper = _Stepper(model, cond, uc, B, x.shape[2:], self._scale, pair=self._pair)
-        s_in = x.new_ones([B])
         evals0 = getattr(self, "aae_evaluations", 0)
         inters, local_losses = [], []
-        mid = (num_sigmas - 1) // 2
-        slot = 0                                                           # the k-th churned step reads draw k
-        for i in self.get_sigma_gen(num_sigmas, init_step=init_step):
-            (e,) = self.step_plan(sig, i, init_step)
-            alpha = 20 * np.sqrt(scales[i])
-            iter_enabled = i in iter_lst
-            thres = float(thres_lst[list(iter_lst).index(i)]) if iter_enabled else 0.0
-            if e.churn != 0.0:
-                ops.axpy_(x, noise[slot], e.churn)
-                slot += 1
-            x = self.attend_and_excite(x, model, s_in * e.sigma, cond, batch, alpha, iter_enabled, thres)
+        mid = (len(sig) - 1) // 2
+        for i, e, x in self._aae_steps(self.attend_and_excite, model, x, cond, batch, sig, init_step, noise):
             den = torch.empty_like(x)
             stepper.step(x, e.sigma, e.sigma_next, emit_maps=True, denoised=den)
             ll = model.loss_fn.get_min_local_loss(stepper.unet.attn_map_cache, batch["mask"], batch["seg_mask"], cond_only=self._pair)
