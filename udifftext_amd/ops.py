@@ -2,6 +2,16 @@
 
 torch is used for device memory and stream plumbing only; every computation below is a launch into
 libudt_kernels.so.  All functions raise if a tensor is not on a GPU — there is no CPU path.
+
+Every wrapper reads "check, allocate, one ``L.check(lib.udt_…)``".  What several of them share has one home each:
+  _drop_sidecars               the sidecar rule (``out.gn_stats`` / ``out.mx8``): whoever overwrites a tensor drops both
+  run_gemm                     the stream-K workspace of every descriptor launch (udt_gemm, udt_gn_silu_conv3x3_fwd, udt_ln_gemm_fwd)
+  _strides                     row strides, then batch strides of [B, N, *] row views (the flash / masked attention argument tails)
+  _masks                       additive mask + key-padding mask of masked_attention / masked_attention_bwd
+  _count_gemm / _count_attn    the WORK_COUNTER amounts bench.py reads
+  _ll_dims / _ll_scratch       checks and scratch of the local_loss_* wrappers
+  _nchw4 / _multistep_coefs    fp32 NCHW operand check and udt_multistep_coefs of the sampler steps
+  conv_out_hw                  a convolution's output size (defined in packing.py: it launches nothing)
 """
 from __future__ import annotations
 
@@ -14,6 +24,7 @@ from typing import NamedTuple, Optional, Sequence
 import torch
 
 from . import lib as L
+from .packing import conv_out_hw  # noqa: F401  (host arithmetic, no launch: kept with the layout helpers, reached as ops.conv_out_hw)
 
 # ---------------------------------------------------------------------------------------- launch context
 # The stream-K kernels need (a) a workspace whose first 4 KiB (slab flags + error word) are zero between launches
@@ -110,33 +121,11 @@ def _bf16(t: torch.Tensor) -> None:
         raise ValueError(f"expected bf16 tensor, got {t.dtype}")
 
 
-# ------------------------------------------------------------------------------------------------ GEMM
-def gemm_desc(**kw) -> L.GemmDesc:
-    d = L.GemmDesc()
-    d.batch = 1
-    d.alpha = 1.0
-    d.cu_share = _ctx.cu_share
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
-
-
-def run_gemm(d: L.GemmDesc, device, fused_gn: bool = False) -> None:
-    lib = L.load()
-    need = lib.udt_gemm_workspace_bytes(C.byref(d))
-    ws_ptr, ws_bytes = None, 0
-    if need:
-        ws = _ws(need, device)
-        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
-    if fused_gn:
-        L.check(lib.udt_gn_silu_conv3x3_fwd(C.byref(d), ws_ptr, ws_bytes, _stream()), "udt_gn_silu_conv3x3_fwd")
-    else:
-        L.check(lib.udt_gemm(C.byref(d), ws_ptr, ws_bytes, _stream()), "udt_gemm")
-
-
-GN_STRIP = True       # one-launch strip GroupNorm where the shape allows (tests switch it off to compare with the two-kernel path)
-
-
+# -------------------------------------------------------------------------------------------- sidecars
+# A producer hangs what its epilogue emitted next to its result on the result tensor: the column statistics (``out.gn_stats``) and
+# the MX8 twin (``out.mx8``).  A consumer trusts what it finds there, so: an op ATTACHES only what its own launch emits, and
+# every op DROPS both sidecars of a caller-visible bf16 tensor it is about to overwrite (an ``out=`` argument, the operand of an
+# in-place op; a fresh allocation carries none).  A view is a new tensor object: hipnn.carry_stats / carry_mx8 hand them over.
 class GnStats(NamedTuple):
     """column statistics a producer's epilogue emitted for its output (udt_gemm_desc.colstats): fp32
     [slots, C, 2] = per-(row slot, channel) (sum, sum of squares); a sample owns ``slots_per_sample`` consecutive slots"""
@@ -146,27 +135,6 @@ class GnStats(NamedTuple):
 
 def gn_stats_of(t: Optional[torch.Tensor]) -> Optional[GnStats]:
     return getattr(t, "gn_stats", None) if t is not None else None
-
-
-def _attach_colstats(d: L.GemmDesc, out: torch.Tensor, n_cols: int, rows_per_batch: int) -> bool:
-    """ask the library whether this problem can emit column statistics; if so allocate them and point the
-    descriptor at them (the tensor rides on ``out.gn_stats``)"""
-    lib = L.load()
-    rows = lib.udt_gemm_colstats_rows(C.byref(d))
-    if rows <= 0:
-        return False
-    slots = lib.udt_gemm_colstats_slots(C.byref(d))
-    st = torch.empty((slots, n_cols, 2), dtype=torch.float32, device=out.device)
-    d.colstats = st.data_ptr()
-    out.gn_stats = GnStats(st, rows_per_batch // rows)
-    return True
-
-
-def _drop_stale_stats(out: Optional[torch.Tensor]) -> None:
-    """a caller-provided ``out=`` tensor may still carry the statistics of an earlier launch into it: this launch emits none,
-    so a GroupNorm reading ``out.gn_stats`` afterwards must not find the old ones"""
-    if out is not None and getattr(out, "gn_stats", None) is not None:
-        del out.gn_stats
 
 
 class Mx8Act(NamedTuple):
@@ -184,6 +152,68 @@ class Mx8Act(NamedTuple):
 def mx8_of(t: Optional[torch.Tensor]) -> Optional[Mx8Act]:
     """the MX8 twin a producer attached to its bf16 result (``out.mx8``), if any"""
     return getattr(t, "mx8", None) if t is not None else None
+
+
+def _drop_sidecars(t: torch.Tensor) -> torch.Tensor:
+    """``t`` is about to be overwritten: what an earlier launch into it left on it describes data that is gone (-> t)"""
+    attrs = vars(t)
+    attrs.pop("gn_stats", None)
+    attrs.pop("mx8", None)
+    return t
+
+
+# ------------------------------------------------------------------------------------------------ GEMM
+def gemm_desc(**kw) -> L.GemmDesc:
+    d = L.GemmDesc()
+    d.batch = 1
+    d.alpha = 1.0
+    d.cu_share = _ctx.cu_share
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def run_gemm(d: L.GemmDesc, device, fused_gn: bool = False, entry: str = "udt_gemm", check: bool = True) -> int:
+    """launch ``entry`` (fused_gn: udt_gn_silu_conv3x3_fwd) on ``d`` with the stream-K workspace its plan asks for.
+    check=False hands the status back for the caller to explain"""
+    if fused_gn:
+        entry = "udt_gn_silu_conv3x3_fwd"
+    lib = L.load()
+    need = lib.udt_gemm_workspace_bytes(C.byref(d))
+    ws_ptr, ws_bytes = None, 0
+    if need:
+        ws = _ws(need, device)
+        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
+    rc = getattr(lib, entry)(C.byref(d), ws_ptr, ws_bytes, _stream())
+    if check:
+        L.check(rc, entry)
+    return rc
+
+
+def _count_gemm(kind: str, flops: float, nbytes: Optional[float] = None) -> None:
+    """one GEMM launch for bench.py's roofline (call under ``if WORK_COUNTER is not None``); kind = "gemm" | "gemm_fp8";
+    nbytes = None: the launch counts no bytes"""
+    count_work(kind, flops)
+    if nbytes is not None:
+        count_work(kind + "_bytes", nbytes)
+    count_work(kind + "_launches", 1.0)
+
+
+GN_STRIP = True       # one-launch strip GroupNorm where the shape allows (tests switch it off to compare with the two-kernel path)
+
+
+def _attach_colstats(d: L.GemmDesc, out: torch.Tensor, n_cols: int, rows_per_batch: int) -> bool:
+    """ask the library whether this problem can emit column statistics; if so allocate them and point the
+    descriptor at them (the tensor rides on ``out.gn_stats``)"""
+    lib = L.load()
+    rows = lib.udt_gemm_colstats_rows(C.byref(d))
+    if rows <= 0:
+        return False
+    slots = lib.udt_gemm_colstats_slots(C.byref(d))
+    st = torch.empty((slots, n_cols, 2), dtype=torch.float32, device=out.device)
+    d.colstats = st.data_ptr()
+    out.gn_stats = GnStats(st, rows_per_batch // rows)
+    return True
 
 
 def _mx8_alloc(M: int, cols: int, device) -> Mx8Act:
@@ -233,26 +263,24 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
             out = torch.empty((M // rows_per_batch, N, rows_per_batch), dtype=dt, device=x.device)
         else:
             out = torch.empty((M, n_cols), dtype=dt, device=x.device)
+    else:
+        _drop_sidecars(out)
     ldo = out.stride(0) if not (flags & L.GEMM_TRANSPOSED) else 0
     d = gemm_desc(a=_ptr(x2), w=_ptr(w), bias=_ptr(bias), residual=_ptr(residual), rowvec=_ptr(rowvec), out=_ptr(out),
                   M=M, N=N, K=K, lda=x2.stride(0), ldo=ldo, ldr=(residual.stride(0) if residual is not None else 0),
                   rows_per_batch=rows_per_batch, ld_rowvec=(rowvec.stride(0) if rowvec is not None else 0), flags=flags,
                   alpha=alpha)
-    if not (colstats and rows_per_batch > 0 and out.is_contiguous() and _attach_colstats(d, out, n_cols, rows_per_batch)):
-        _drop_stale_stats(out)
+    if colstats and rows_per_batch > 0 and out.is_contiguous():
+        _attach_colstats(d, out, n_cols, rows_per_batch)
     q8 = None
     if emit_q8 and not (flags & (L.GEMM_OUT_F32 | L.GEMM_TRANSPOSED | L.GEMM_GEGLU)) and d.colstats is None and rowvec is None:
         q8 = _attach_q8(d, M, n_cols, x.device, emit_rowstats)      # (None: the plan has no emitting epilogue)
     run_gemm(d, x.device)
-    if getattr(out, "mx8", None) is not None:
-        del out.mx8
     if q8 is not None:
         out.mx8 = q8
     if WORK_COUNTER is not None:
-        count_work("gemm", 2.0 * M * N * K)
-        count_work("gemm_bytes", 2.0 * (M * K + N * K) + out.numel() * out.element_size()
-                   + (2.0 * M * n_cols if residual is not None else 0.0))
-        count_work("gemm_launches", 1.0)
+        _count_gemm("gemm", 2.0 * M * N * K, 2.0 * (M * K + N * K) + out.numel() * out.element_size()
+                    + (2.0 * M * n_cols if residual is not None else 0.0))
     return out
 
 
@@ -274,7 +302,9 @@ def linear_mx8(x: Mx8Act, wq: torch.Tensor, colscale: torch.Tensor, bias: Option
     geglu = bool(flags & L.GEMM_GEGLU)
     n_cols = N // 2 if geglu else N
     only_q8 = emit_q8 and not want_bf16
-    if out is None and not only_q8:
+    if out is not None:
+        _drop_sidecars(out)
+    elif not only_q8:
         out = torch.empty((M, n_cols), dtype=torch.bfloat16, device=xq.device)
     d = gemm_desc(a=_ptr(xq), w=_ptr(wq), bias=_ptr(ln_c if ln_c is not None else bias), residual=_ptr(residual),
                   out=_ptr(out), M=M, N=N, K=K, lda=K, ldo=(out.stride(0) if out is not None else 0),
@@ -286,20 +316,16 @@ def linear_mx8(x: Mx8Act, wq: torch.Tensor, colscale: torch.Tensor, bias: Option
         assert x.stats.dtype == torch.float32 and x.stats.is_contiguous() and x.stats.shape[1:] == (M, 2)
         d.ln_colsum, d.ln_eps = _ptr(ln_s), eps
         d.rowstat_in, d.rowstat_in_parts = _ptr(x.stats), x.stats.shape[0]
-    if out is not None and not (colstats and rows_per_batch > 0 and out.is_contiguous()
-                                and _attach_colstats(d, out, n_cols, rows_per_batch)):
-        _drop_stale_stats(out)
+    if out is not None and colstats and rows_per_batch > 0 and out.is_contiguous():
+        _attach_colstats(d, out, n_cols, rows_per_batch)
     q8 = None
     if emit_q8:
         q8 = _attach_q8(d, M, n_cols, xq.device, emit_rowstats and not geglu, fixed=q8_fixed)
         if q8 is None:
             raise L.UdtError(f"udt_gemm has no MX8-emitting plan for M={M} N={N} K={K} flags={flags:#x}")
     run_gemm(d, xq.device)
-    if out is not None and getattr(out, "mx8", None) is not None:
-        del out.mx8
     if WORK_COUNTER is not None:
-        count_work("gemm_fp8", 2.0 * M * N * K)
-        count_work("gemm_fp8_launches", 1.0)
+        _count_gemm("gemm_fp8", 2.0 * M * N * K)
     if only_q8:
         return q8
     if q8 is not None:
@@ -323,7 +349,9 @@ def ln_linear(x: torch.Tensor, w_folded: torch.Tensor, c: torch.Tensor, s: torch
     N = w_folded.shape[0] if n_out is None else n_out
     n_cols = N // 2 if (flags & L.GEMM_GEGLU) else N
     only_q8 = emit_q8 and not want_bf16
-    if out is None and not only_q8:
+    if out is not None:
+        _drop_sidecars(out)
+    elif not only_q8:
         out = torch.empty((M, n_cols), dtype=torch.bfloat16, device=x.device)
     d = gemm_desc(a=_ptr(x2), w=_ptr(w_folded), bias=_ptr(c), residual=_ptr(residual), out=_ptr(out), M=M, N=N, K=K,
                   lda=x2.stride(0), ldo=(out.stride(0) if out is not None else 0),
@@ -336,13 +364,7 @@ def ln_linear(x: torch.Tensor, w_folded: torch.Tensor, c: torch.Tensor, s: torch
             if q8_or_none:
                 return None
             raise L.UdtError(f"udt_ln_gemm_fwd has no MX8-emitting plan for M={M} N={N} K={K}")
-    lib = L.load()
-    need = lib.udt_gemm_workspace_bytes(C.byref(d))
-    ws_ptr, ws_bytes = None, 0
-    if need:
-        ws = _ws(need, x.device)
-        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
-    rc = lib.udt_ln_gemm_fwd(C.byref(d), ws_ptr, ws_bytes, _stream())
+    rc = run_gemm(d, x.device, entry="udt_ln_gemm_fwd", check=False)
     if rc in (-1, -2) and x.is_cuda:            # UDT_ERR_BAD_SHAPE / UDT_ERR_BAD_ARG
         # the LayerNorm-folded form exists on the lean kernels only: a problem their plan declines (lean kernels switched off at
         # run time through udt_debug_set, unaligned out / residual pointers, > 2 GiB operands) says so loudly instead of
@@ -352,10 +374,8 @@ def ln_linear(x: torch.Tensor, w_folded: torch.Tensor, c: torch.Tensor, s: torch
                          "set UDT_LN_GEMM=0 to run layernorm + GEMM instead")
     L.check(rc, "udt_ln_gemm_fwd")
     if WORK_COUNTER is not None:
-        count_work("gemm", 2.0 * M * N * K)
-        count_work("gemm_bytes", 2.0 * (M * K + N * K) + (2.0 if out is not None else 0.0) * M * n_cols
-                   + (1.0 * M * n_cols if q8 is not None else 0.0) + (2.0 * M * n_cols if residual is not None else 0.0))
-        count_work("gemm_launches", 1.0)
+        _count_gemm("gemm", 2.0 * M * N * K, 2.0 * (M * K + N * K) + (2.0 if out is not None else 0.0) * M * n_cols
+                    + (1.0 * M * n_cols if q8 is not None else 0.0) + (2.0 * M * n_cols if residual is not None else 0.0))
     if only_q8:
         return q8
     if q8 is not None:
@@ -369,16 +389,13 @@ def bmm_nt(a: torch.Tensor, w: torch.Tensor, *, out: Optional[torch.Tensor] = No
     B, M, K = a.shape
     N = w.shape[1]
     assert a.stride(2) == 1 and w.stride(2) == 1 and w.shape[0] == B and w.shape[2] == K
-    if out is None:
-        out = torch.empty((B, M, N), dtype=torch.bfloat16, device=a.device)
+    out = _drop_sidecars(out) if out is not None else torch.empty((B, M, N), dtype=torch.bfloat16, device=a.device)
     d = gemm_desc(a=_ptr(a), w=_ptr(w), out=_ptr(out), M=M, N=N, K=K, lda=a.stride(1), ldw=w.stride(1),
                   ldo=out.stride(1), batch=B, stride_a=a.stride(0), stride_w=w.stride(0), stride_out=out.stride(0),
                   alpha=alpha)
     run_gemm(d, a.device)
     if WORK_COUNTER is not None:
-        count_work("gemm", 2.0 * B * M * N * K)
-        count_work("gemm_bytes", 2.0 * B * (M * K + N * K + M * N))
-        count_work("gemm_launches", 1.0)
+        _count_gemm("gemm", 2.0 * B * M * N * K, 2.0 * B * (M * K + N * K + M * N))
     return out
 
 
@@ -403,19 +420,20 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         _bf16(x2)
         assert x2.is_contiguous() and x2.shape[:3] == x.shape[:3]
         C2 = x2.shape[3]
-    Hv, Wv = (H * 2, W_ * 2) if upsample else (H, W_)
     if pad is None:
         pad = (ksize // 2, ksize // 2)
-    if out_hw is None:
-        out_hw = ((Hv + 2 * pad[0] - ksize) // stride + 1, (Wv + 2 * pad[1] - ksize) // stride + 1)
-    Ho, Wo = out_hw
+    Ho, Wo = conv_out_hw(H, W_, ksize, stride, pad, upsample) if out_hw is None else out_hw
     N = w.shape[0] if n_out is None else n_out
     K = ksize * ksize * (C1 + C2)
     assert w.shape[1] == K, (w.shape, K)
     M = B * Ho * Wo
-    if out is None and not probe_in_scsh:
+    if probe_in_scsh:
+        pass                                      # (nothing is written)
+    elif out is None:
         dt = torch.float32 if (flags & L.GEMM_OUT_F32) else torch.bfloat16
         out = torch.empty((B, Ho, Wo, N), dtype=dt, device=x.device)
+    else:
+        _drop_sidecars(out)
     d = gemm_desc(a=_ptr(x), a2=_ptr(x2), w=_ptr(w), bias=_ptr(bias), residual=_ptr(residual), rowvec=_ptr(rowvec),
                   out=_ptr(out), M=M, N=N, K=K, lda=0, ldo=(out.stride(2) if out is not None else N),
                   ldr=(residual.stride(2) if residual is not None else 0),
@@ -435,16 +453,26 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         assert in_scsh.dtype == torch.float32 and in_scsh.is_contiguous() and in_scsh.numel() == B * (C1 + C2) * 2
         d.in_scsh = in_scsh.data_ptr()
         d.in_act = int(in_act)
-    if not (colstats and _attach_colstats(d, out, N, Ho * Wo)):
-        _drop_stale_stats(out)
-    if in_scsh is not None:
-        run_gemm(d, x.device, fused_gn=True)
-    else:
-        run_gemm(d, x.device)
+    if colstats:
+        _attach_colstats(d, out, N, Ho * Wo)
+    run_gemm(d, x.device, fused_gn=in_scsh is not None)
     return out
 
 
 # ------------------------------------------------------------------------------------------- attention
+def _strides(*views: Optional[torch.Tensor], between: tuple = ()) -> tuple:
+    """the stride tail of the attention entry points: the row strides of [B, N, *] row views, ``between``, then their batch
+    strides (a view that is None: 0)"""
+    return (*[0 if t is None else t.stride(1) for t in views], *between, *[0 if t is None else t.stride(0) for t in views])
+
+
+def _count_attn(kind: str, flops: float, nbytes: float) -> None:
+    """one attention launch for bench.py's roofline (call under ``if WORK_COUNTER is not None``); kind = "attn" | "attn_fp8" """
+    count_work(kind, flops)
+    count_work(kind + "_bytes", nbytes)
+    count_work(kind + "_launches", 1.0)
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, scale: float,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q,k: [B, N, *] row views whose first heads*64 columns are the head-major projections (last dim
@@ -453,16 +481,11 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, sc
     B, Nq = q.shape[0], q.shape[1]
     Nk = k.shape[1]
     assert q.stride(2) == 1 and k.stride(2) == 1 and vt.stride(2) == 1
-    if out is None:
-        out = torch.empty((B, Nq, heads * 64), dtype=torch.bfloat16, device=q.device)
-    L.check(L.load().udt_attn_fwd(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), B, heads, Nq, Nk,
-                                  q.stride(1), k.stride(1), vt.stride(1), out.stride(1),
-                                  q.stride(0), k.stride(0), vt.stride(0), out.stride(0), scale, _stream()),
+    out = _drop_sidecars(out) if out is not None else torch.empty((B, Nq, heads * 64), dtype=torch.bfloat16, device=q.device)
+    L.check(L.load().udt_attn_fwd(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), B, heads, Nq, Nk, *_strides(q, k, vt, out), scale, _stream()),
             "udt_attn_fwd")
     if WORK_COUNTER is not None:
-        count_work("attn", 4.0 * B * heads * Nq * Nk * 64)
-        count_work("attn_bytes", 2.0 * B * heads * 64 * (2 * Nq + 2 * Nk))
-        count_work("attn_launches", 1.0)
+        _count_attn("attn", 4.0 * B * heads * Nq * Nk * 64, 2.0 * B * heads * 64 * (2 * Nq + 2 * Nk))
     return out
 
 
@@ -475,26 +498,16 @@ def attention_rowv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
     B, Nq = q.shape[0], q.shape[1]
     Nk = k.shape[1]
     assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1 and v.shape[1] == Nk
-    if out is None:
-        out = torch.empty((B, Nq, heads * 64), dtype=torch.bfloat16, device=q.device)
-    if getattr(out, "mx8", None) is not None:
-        del out.mx8
+    out = _drop_sidecars(out) if out is not None else torch.empty((B, Nq, heads * 64), dtype=torch.bfloat16, device=q.device)
+    args = (_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk, *_strides(q, k, v, out), scale)
     if emit_q8 and heads % 2 == 0 and out.is_contiguous():
         q8 = _mx8_alloc(B * Nq, heads * 64, q.device)
-        L.check(L.load().udt_attn_rowv_q8_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk,
-                                              q.stride(1), k.stride(1), v.stride(1), out.stride(1),
-                                              q.stride(0), k.stride(0), v.stride(0), out.stride(0), scale,
-                                              _ptr(q8.data), _ptr(q8.scale), heads * 64, _stream()), "udt_attn_rowv_q8_fwd")
+        L.check(L.load().udt_attn_rowv_q8_fwd(*args, _ptr(q8.data), _ptr(q8.scale), heads * 64, _stream()), "udt_attn_rowv_q8_fwd")
         out.mx8 = q8
     else:
-        L.check(L.load().udt_attn_rowv_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk,
-                                           q.stride(1), k.stride(1), v.stride(1), out.stride(1),
-                                           q.stride(0), k.stride(0), v.stride(0), out.stride(0), scale, _stream()),
-                "udt_attn_rowv_fwd")
+        L.check(L.load().udt_attn_rowv_fwd(*args, _stream()), "udt_attn_rowv_fwd")
     if WORK_COUNTER is not None:
-        count_work("attn", 4.0 * B * heads * Nq * Nk * 64)
-        count_work("attn_bytes", 2.0 * B * heads * 64 * (2 * Nq + 2 * Nk))
-        count_work("attn_launches", 1.0)
+        _count_attn("attn", 4.0 * B * heads * Nq * Nk * 64, 2.0 * B * heads * 64 * (2 * Nq + 2 * Nk))
     return out
 
 
@@ -508,21 +521,16 @@ def attention_mx8(qkv: Mx8Act, batch: int, heads: int, scale: float, v_mul: floa
     assert qkv.data.dtype == torch.uint8 and qkv.data.is_contiguous() and ld8 >= 3 * C_ and M % batch == 0
     assert qkv.scale.dtype == torch.int32 and qkv.scale.is_contiguous() and qkv.scale.shape == ((ld8 + 127) // 128, M)
     N = M // batch
-    if out is None:
-        out = torch.empty((batch, N, C_), dtype=torch.bfloat16, device=qkv.data.device)
+    out = _drop_sidecars(out) if out is not None else torch.empty((batch, N, C_), dtype=torch.bfloat16, device=qkv.data.device)
     assert out.is_contiguous()
-    if getattr(out, "mx8", None) is not None:
-        del out.mx8
-    q8 = _mx8_alloc(M, C_, qkv.data.device) if emit_q8 else None
+    q8 =_mx8_alloc(M, C_, qkv.data.device) if emit_q8 else None
     L.check(L.load().udt_attn_mx8_fwd(_ptr(qkv.data), _ptr(qkv.scale), _ptr(out), batch, heads, N, ld8, out.stride(1), scale,
                                       1.0 / v_mul, _ptr(q8.data) if q8 else None, _ptr(q8.scale) if q8 else None, C_, _stream()),
             "udt_attn_mx8_fwd")
     if q8 is not None:
         out.mx8 = q8
     if WORK_COUNTER is not None:
-        count_work("attn_fp8", 4.0 * batch * heads * N * N * 64)
-        count_work("attn_fp8_bytes", 1.0 * batch * heads * 64 * 3 * N + 2.0 * batch * heads * 64 * N)
-        count_work("attn_fp8_launches", 1.0)
+        _count_attn("attn_fp8", 4.0 * batch * heads * N * N * 64, 1.0 * batch * heads * 64 * 3 * N + 2.0 * batch * heads * 64 * N)
     return out
 
 
@@ -537,25 +545,17 @@ def attention_d512(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: flo
     Nk = k.shape[1]
     assert q.shape[2] == 512 and k.shape[2] == 512 and v.shape[2] == 512 and v.shape[1] == Nk
     assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
-    if out is None:
-        out = torch.empty((B, Nq, 512), dtype=torch.bfloat16, device=q.device)
+    out = _drop_sidecars(out) if out is not None else torch.empty((B, Nq, 512), dtype=torch.bfloat16, device=q.device)
     lib = L.load()
     need = int(lib.udt_attn512_workspace_bytes(B, Nq, Nk)) if key_split else 0
+    args = (_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, Nq, Nk, *_strides(q, k, v, out), scale)
     if need:
         scratch = torch.empty((need,), dtype=torch.uint8, device=q.device)
-        L.check(lib.udt_attn512_split_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, Nq, Nk,
-                                          q.stride(1), k.stride(1), v.stride(1), out.stride(1),
-                                          q.stride(0), k.stride(0), v.stride(0), out.stride(0), scale, _ptr(scratch), need, _stream()),
-                "udt_attn512_split_fwd")
+        L.check(lib.udt_attn512_split_fwd(*args, _ptr(scratch), need, _stream()), "udt_attn512_split_fwd")
     else:
-        L.check(lib.udt_attn512_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, Nq, Nk,
-                                    q.stride(1), k.stride(1), v.stride(1), out.stride(1),
-                                    q.stride(0), k.stride(0), v.stride(0), out.stride(0), scale, _stream()),
-                "udt_attn512_fwd")
+        L.check(lib.udt_attn512_fwd(*args, _stream()), "udt_attn512_fwd")
     if WORK_COUNTER is not None:
-        count_work("attn", 4.0 * B * Nq * Nk * 512)
-        count_work("attn_bytes", 2.0 * B * 512 * (2 * Nq + 2 * Nk))
-        count_work("attn_launches", 1.0)
+        _count_attn("attn", 4.0 * B * Nq * Nk * 512, 2.0 * B * 512 * (2 * Nq + 2 * Nk))
     return out
 
 
@@ -568,13 +568,23 @@ def xattention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, he
     assert q.is_contiguous() or (q.stride(2) == 1 and q.stride(0) == Nq * q.stride(1))
     assert k.stride(2) == 1 and v.stride(2) == 1 and k.stride(1) == v.stride(1)
     assert k.stride(0) == Lc * k.stride(1) and v.stride(0) == Lc * v.stride(1)
-    if out is None:
-        out = torch.empty((B, Nq, heads * head_dim), dtype=torch.bfloat16, device=q.device)
+    out = _drop_sidecars(out) if out is not None else torch.empty((B, Nq, heads * head_dim), dtype=torch.bfloat16, device=q.device)
     if probs is not None:
         assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.numel() == B * heads * Nq * Lc
     L.check(L.load().udt_xattn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(probs), B, heads, head_dim, Nq, Lc,
                                    q.stride(1), k.stride(1), out.stride(1), scale, _stream()), "udt_xattn_fwd")
     return out
+
+
+def _masks(mask: Optional[torch.Tensor], key_padding_mask: Optional[torch.Tensor], B: int, Nq: int, Lk: int) -> tuple:
+    """the masks in the form udt_mattn_fwd / udt_mattn_bwd read: additive fp32 [Nq, Lk], key padding uint8 [B, Lk], contiguous"""
+    if mask is not None:
+        mask = mask.float().contiguous()
+        assert mask.shape == (Nq, Lk)
+    if key_padding_mask is not None:
+        key_padding_mask = key_padding_mask.to(torch.uint8).contiguous()
+        assert key_padding_mask.shape == (B, Lk)
+    return mask, key_padding_mask
 
 
 def masked_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float,
@@ -588,17 +598,10 @@ def masked_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
     Lk = k.shape[1]
     D = Cq // heads
     assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
-    if out is None:
-        out = torch.empty((B, Nq, heads * D), dtype=torch.bfloat16, device=q.device)
-    if mask is not None:
-        mask = mask.float().contiguous()
-        assert mask.shape == (Nq, Lk)
-    if key_padding_mask is not None:
-        key_padding_mask = key_padding_mask.to(torch.uint8).contiguous()
-        assert key_padding_mask.shape == (B, Lk)
+    out = _drop_sidecars(out) if out is not None else torch.empty((B, Nq, heads * D), dtype=torch.bfloat16, device=q.device)
+    mask, key_padding_mask = _masks(mask, key_padding_mask, B, Nq, Lk)
     L.check(L.load().udt_mattn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(mask), _ptr(key_padding_mask), B, heads, D,
-                                   Nq, Lk, q.stride(1), k.stride(1), v.stride(1), out.stride(1), Lk,
-                                   q.stride(0), k.stride(0), v.stride(0), out.stride(0), scale, _stream()), "udt_mattn_fwd")
+                                   Nq, Lk, *_strides(q, k, v, out, between=(Lk,)), scale, _stream()), "udt_mattn_fwd")
     return out
 
 
@@ -637,13 +640,10 @@ def tattn_fused(x: torch.Tensor, tables: Optional[TattnTables], bias: torch.Tens
     _bf16(x)
     assert x.is_contiguous()
     B, N, Cc = x.shape
-    if out is None:
-        out = torch.empty_like(x)
+    out = _drop_sidecars(out) if out is not None else torch.empty_like(x)
     assert out.is_contiguous()
     if tables is not None:
         assert tables.A.is_contiguous() and tables.sc.is_contiguous() and tables.BmT.is_contiguous() and tables.A.shape[0] == B
-    if getattr(out, "mx8", None) is not None:
-        del out.mx8
     parts = L.load().udt_tattn_rowstat_parts(B, N, Cc) if emit_q8 else 0
     if parts > 0:
         q = _mx8_alloc(B * N, Cc, x.device)
@@ -663,6 +663,7 @@ def softmax_rows_(x: torch.Tensor) -> torch.Tensor:
     _bf16(x)
     assert x.is_contiguous()
     cols = x.shape[-1]
+    _drop_sidecars(x)
     L.check(L.load().udt_softmax_rows(_ptr(x), x.numel() // cols, cols, cols, _stream()), "udt_softmax_rows")
     return x
 
@@ -682,8 +683,7 @@ def group_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups:
         C2 = x2.shape[-1]
     HW = x.numel() // (B * C1)
     lib = L.load()
-    if out is None:
-        out = torch.empty(x.shape[:-1] + (C1 + C2,), dtype=torch.bfloat16, device=x.device)
+    out = _drop_sidecars(out) if out is not None else torch.empty(x.shape[:-1] + (C1 + C2,), dtype=torch.bfloat16, device=x.device)
     if GN_STRIP and lib.udt_gn_strip_ok(B, HW, C1, C2, groups):      # one launch, second read out of L2
         L.check(lib.udt_gn_strip(_ptr(x), _ptr(x2), _ptr(out), _ptr(gamma), _ptr(beta), B, HW, C1, C2, groups, eps,
                                  1 if silu else 0, _stream()), "udt_gn_strip")
@@ -727,8 +727,7 @@ def group_norm_from_stats(x: torch.Tensor, st1: GnStats, gamma: torch.Tensor, be
         assert x2.is_contiguous() and x2.shape[:-1] == x.shape[:-1] and st2 is not None
         C2 = x2.shape[-1]
     HW = x.numel() // (B * C1)
-    if out is None:
-        out = torch.empty(x.shape[:-1] + (C1 + C2,), dtype=torch.bfloat16, device=x.device)
+    out = _drop_sidecars(out) if out is not None else torch.empty(x.shape[:-1] + (C1 + C2,), dtype=torch.bfloat16, device=x.device)
     if gn_strip_ok(B, HW, C1, C2, groups):          # small levels: one launch, the strip kernel without its statistics pass
         L.check(L.load().udt_gn_strip_stats(_ptr(x), _ptr(x2), _ptr(out), _ptr(st1.data), st1.slots_per_sample,
                                             _ptr(st2.data) if st2 is not None else None,
@@ -746,16 +745,34 @@ def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: fl
     _bf16(x)
     assert x.is_contiguous()
     Cc = x.shape[-1]
-    if out is None:
-        out = torch.empty_like(x)
+    out = _drop_sidecars(out) if out is not None else torch.empty_like(x)
     L.check(L.load().udt_layernorm(_ptr(x), _ptr(out), _ptr(gamma), _ptr(beta), x.numel() // Cc, Cc, eps, _stream()),
             "udt_layernorm")
     return out
 
 
 # ---------------------------------------------------------------------------------------- elementwise
+def _nchw4(shape, *tensors: Optional[torch.Tensor]) -> None:
+    """the latents of a sampler step (a None is an absent term): fp32 NCHW [B,4,h,w], contiguous"""
+    B, _, h, w = shape
+    for t in tensors:
+        if t is not None:
+            assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, 4, h, w), "fp32 NCHW [B,4,h,w]"
+
+
+def _multistep_coefs(c_out: float, scale: float, sigma: float, coefs: Sequence[float], hist: Sequence[torch.Tensor]) -> L.MultistepCoefs:
+    """udt_multistep_coefs: k[j] = coefs[j]; hist[j + 1] = the j-th older derivative (slot 0 is d itself)"""
+    k = L.MultistepCoefs(c_out, scale, sigma, len(coefs))
+    for j, c in enumerate(coefs):
+        k.k[j] = c
+    for j, t in enumerate(hist):
+        k.hist[j + 1] = _ptr(t)
+    return k
+
+
 def unet_input(x: torch.Tensor, xin: torch.Tensor, c_in: float) -> None:
     B, _, h, w = x.shape
+    _drop_sidecars(xin)
     L.check(L.load().udt_unet_input(_ptr(x), _ptr(xin), B, h * w, xin.shape[-1], c_in, _stream()), "udt_unet_input")
 
 
@@ -763,8 +780,9 @@ def unet_input_churn(x: torch.Tensor, noise: torch.Tensor, xin: torch.Tensor, c_
     """one launch of udt_unet_input_churn: x <- x + kn*noise in place (x, noise: fp32 NCHW [B,4,h,w] contiguous, distinct), then
     unet_input on the stored x"""
     B, _, h, w = x.shape
-    for t in (x, noise):
-        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, 4, h, w), "fp32 NCHW [B,4,h,w]"
+    assert noise is not None
+    _nchw4(x.shape, x, noise)
+    _drop_sidecars(xin)
     L.check(L.load().udt_unet_input_churn(_ptr(x), _ptr(noise), _ptr(xin), B, h * w, xin.shape[-1], c_in, kn, _stream()),
             "udt_unet_input_churn")
 
@@ -788,9 +806,7 @@ def cfg_sampler_step(xin: torch.Tensor, eps: torch.Tensor, c_out: float, scale: 
     xin / aux / prev / noise / out / denoised: fp32 NCHW [B,4,h,w] contiguous; out defaults to xin (in place)."""
     B, _, h, w = xin.shape
     out = xin if out is None else out
-    for t in (xin, aux, prev, noise, out, denoised):
-        if t is not None:
-            assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, 4, h, w), "fp32 NCHW [B,4,h,w]"
+    _nchw4(xin.shape, xin, aux, prev, noise, out, denoised)
     assert eps.dtype == torch.float32 and eps.is_contiguous() and tuple(eps.shape[:-1]) == (2 * B, h, w) and eps.shape[-1] >= 4
     k = L.SamplerCoefs(kx, kd, ka, kp, kn, c_out, scale)
     L.check(L.load().udt_cfg_sampler_step(_ptr(xin), _ptr(eps), _ptr(aux), _ptr(prev), _ptr(noise), _ptr(out), _ptr(denoised),
@@ -809,15 +825,10 @@ def cfg_multistep_step(xin: torch.Tensor, eps: torch.Tensor, c_out: float, scale
     out = xin if out is None else out
     n = len(coefs)
     assert 1 <= n <= L.MULTISTEP_MAX and len(hist) == n - 1, "n = len(coefs) in 1..8 and len(hist) = n - 1"
-    assert d_out is not None, "d_out is required"
-    for t in (xin, out, d_out, *hist):
-        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, 4, h, w), "fp32 NCHW [B,4,h,w]"
+    assert d_out is not None and all(t is not None for t in hist), "d_out and every hist tensor are required"
+    _nchw4(xin.shape, xin, out, d_out, *hist)
     assert eps.dtype == torch.float32 and eps.is_contiguous() and tuple(eps.shape[:-1]) == (2 * B, h, w) and eps.shape[-1] >= 4
-    k = L.MultistepCoefs(c_out, scale, sigma, n)
-    for j, c in enumerate(coefs):
-        k.k[j] = c
-    for j, t in enumerate(hist):
-        k.hist[j + 1] = _ptr(t)
+    k = _multistep_coefs(c_out, scale, sigma, coefs, hist)
     L.check(L.load().udt_cfg_multistep_step(_ptr(xin), _ptr(eps), _ptr(out), _ptr(d_out), B, h * w, eps.shape[-1], k,
                                             _stream()), "udt_cfg_multistep_step")
     return out
@@ -849,6 +860,7 @@ def precond_unet_input(x: torch.Tensor, xin: torch.Tensor, c_in: float, pair: bo
     if xin.dtype != torch.bfloat16 or not xin.is_contiguous() or tuple(xin.shape[:-1]) != (rows, h, w):
         raise ValueError(f"precond_unet_input: xin must be bf16 [{rows}, {h}, {w}, cpad] ({'CFG pair' if pair else 'unguided'}), "
                          f"got {tuple(xin.shape)}")
+    _drop_sidecars(xin)
     L.check(L.load().udt_precond_unet_input(_ptr(x), _ptr(noise), _ptr(xin), B, h * w, xin.shape[-1], c_in, kn, int(pair),
                                             _stream()), "udt_precond_unet_input")
 
@@ -883,11 +895,7 @@ def precond_multistep_step(xin: torch.Tensor, f: torch.Tensor, c_skip: float, c_
     if not (1 <= n <= L.MULTISTEP_MAX and len(hist) == n - 1) or d_out is None:
         raise ValueError("precond_multistep_step: n = len(coefs) in 1..8, len(hist) = n - 1 and d_out is required")
     B, hw, ld = _check_step_args(xin, f, pair, "precond_multistep_step", out, d_out, *hist)
-    k = L.MultistepCoefs(c_out, scale, sigma, n)
-    for j, c in enumerate(coefs):
-        k.k[j] = c
-    for j, t in enumerate(hist):
-        k.hist[j + 1] = _ptr(t)
+    k = _multistep_coefs(c_out, scale, sigma, coefs, hist)
     L.check(L.load().udt_precond_multistep_step(_ptr(xin), _ptr(f), _ptr(out), _ptr(d_out), B, hw, ld, k, c_skip, int(pair),
                                                 _stream()), "udt_precond_multistep_step")
     return out
@@ -923,6 +931,7 @@ def nhwc_to_nchw(x: torch.Tensor, channels: int) -> torch.Tensor:
 def nhwc_set_channels(src: torch.Tensor, dst: torch.Tensor, c0: int) -> None:
     assert src.dtype == torch.float32 and src.is_contiguous() and dst.dtype == torch.bfloat16 and dst.is_contiguous()
     B, Cc, H, W_ = src.shape
+    _drop_sidecars(dst)
     L.check(L.load().udt_nhwc_set_channels(_ptr(src), _ptr(dst), B, Cc, H * W_, dst.shape[-1], c0, _stream()),
             "udt_nhwc_set_channels")
 
@@ -1017,17 +1026,11 @@ def masked_attention_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d_o:
         if t is not None:
             _bf16(t)
             assert t.stride(2) == 1
-    if mask is not None:
-        mask = mask.float().contiguous()
-        assert mask.shape == (Nq, Lk)
-    if key_padding_mask is not None:
-        key_padding_mask = key_padding_mask.to(torch.uint8).contiguous()
-        assert key_padding_mask.shape == (B, Lk)
+            _drop_sidecars(t)
+    mask, key_padding_mask = _masks(mask, key_padding_mask, B, Nq, Lk)
     L.check(L.load().udt_mattn_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(mask), _ptr(key_padding_mask),
-                                   B, heads, D, Nq, Lk, q.stride(1), k.stride(1), v.stride(1), d_o.stride(1),
-                                   dq.stride(1) if dq is not None else 0, dk.stride(1), dv.stride(1), Lk,
-                                   q.stride(0), k.stride(0), v.stride(0), d_o.stride(0), dq.stride(0) if dq is not None else 0,
-                                   dk.stride(0), dv.stride(0), scale, _stream()), "udt_mattn_bwd")
+                                   B, heads, D, Nq, Lk, *_strides(q, k, v, d_o, dq, dk, dv, between=(Lk,)), scale, _stream()),
+            "udt_mattn_bwd")
     return dq, dk, dv
 
 
@@ -1070,14 +1073,28 @@ def ocr_ce(logits: torch.Tensor, targets: torch.Tensor, n_chars: torch.Tensor, w
     return loss, d_logits
 
 
+def _ll_dims(probs: torch.Tensor, B: int, heads: int, loss: Optional[torch.Tensor], d_probs: Optional[torch.Tensor] = None,
+             tiled: bool = True) -> tuple:
+    """the checks of the local_loss_* wrappers -> (n, Lc): probs [n * heads, tokens, Lc] contiguous, scored against B masks (tiled:
+    n a multiple of B, else n == B); loss fp32 [n] (None only next to a d_probs); d_probs fp32, like probs"""
+    n = probs.shape[0] // heads
+    assert probs.is_contiguous() and (n % B == 0 if tiled else probs.shape[0] == B * heads)
+    assert d_probs is not None if loss is None else (loss.is_contiguous() and loss.numel() == n)
+    assert d_probs is None or (d_probs.dtype == torch.float32 and d_probs.is_contiguous() and d_probs.shape == probs.shape)
+    return n, probs.shape[-1]
+
+
+def _ll_scratch(probs: torch.Tensor, *shape: int) -> torch.Tensor:
+    """the partial sums one local-loss launch keeps per (sample, segment)"""
+    return torch.empty(shape, dtype=torch.float32, device=probs.device)
+
+
 def local_loss_accumulate(probs: torch.Tensor, mask: torch.Tensor, seg_mask: torch.Tensor, gk9: torch.Tensor,
                           loss: torch.Tensor, heads: int, size: int) -> None:
     """loss [n] += per-layer local-loss term of n = probs.shape[0] / heads samples; sample i is scored against
     mask[i % B] / seg_mask[i % B] (B = mask.shape[0]; n a multiple of B: tiled candidates, or the uncond ‖ cond halves)"""
     B = mask.shape[0]
-    n = probs.shape[0] // heads
-    Lc = probs.shape[-1]
-    assert probs.is_contiguous() and loss.is_contiguous() and loss.numel() == n and n % B == 0
+    n, Lc = _ll_dims(probs, B, heads, loss)
     L.check(L.load().udt_local_loss_tiled(_ptr(probs), _ptr(mask), _ptr(seg_mask), _ptr(gk9), _ptr(loss), n, B, heads, size, Lc,
                                           seg_mask.shape[1], mask.shape[2], mask.shape[3], _stream()), "udt_local_loss_tiled")
 
@@ -1096,10 +1113,8 @@ def local_loss_accumulate_hw(probs: torch.Tensor, mask: torch.Tensor, seg_mask: 
     (context token, sample)"""
     h, w = _check_map_hw(probs, hw, "local_loss_accumulate_hw")
     B = mask.shape[0]
-    n = probs.shape[0] // heads
-    Lc = probs.shape[-1]
-    assert probs.is_contiguous() and loss.is_contiguous() and loss.numel() == n and n % B == 0
-    scratch = torch.empty((n, seg_mask.shape[1], 2), dtype=torch.float32, device=probs.device)
+    n, Lc = _ll_dims(probs, B, heads, loss)
+    scratch = _ll_scratch(probs, n, seg_mask.shape[1], 2)
     L.check(L.load().udt_local_loss_tiled_hw(_ptr(probs), _ptr(mask), _ptr(seg_mask), _ptr(gk9), _ptr(loss), _ptr(scratch), n, B, heads,
                                              h, w, Lc, seg_mask.shape[1], mask.shape[2], mask.shape[3], _stream()),
             "udt_local_loss_tiled_hw")
@@ -1108,6 +1123,7 @@ def local_loss_accumulate_hw(probs: torch.Tensor, mask: torch.Tensor, seg_mask: 
 def add_(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     _bf16(x); _bf16(y)
     assert x.is_contiguous() and y.is_contiguous() and x.numel() == y.numel()
+    _drop_sidecars(x)
     L.check(L.load().udt_add_bf16(_ptr(x), _ptr(y), x.numel(), _stream()), "udt_add_bf16")
     return x
 
@@ -1116,8 +1132,7 @@ def bias_add(x: torch.Tensor, bias: torch.Tensor, out: Optional[torch.Tensor] = 
     """out[..., c] = x[..., c] + bias[c]  (bf16 rows, fp32 bias)"""
     _bf16(x)
     Cc = x.shape[-1]
-    if out is None:
-        out = torch.empty_like(x)
+    out = _drop_sidecars(out) if out is not None else torch.empty_like(x)
     assert x.is_contiguous() and out.is_contiguous() and bias.dtype == torch.float32 and bias.numel() >= Cc
     L.check(L.load().udt_bias_add_bf16(_ptr(x), _ptr(bias), _ptr(out), x.numel() // Cc, Cc, _stream()), "udt_bias_add_bf16")
     return out
@@ -1163,11 +1178,8 @@ def local_loss_bwd(probs: torch.Tensor, mask: torch.Tensor, seg_mask: torch.Tens
                    loss: Optional[torch.Tensor], heads: int, size: int, weight: float) -> None:
     """d_probs += weight * d(local-loss term of this layer) / d probs (and loss += the term): udt_local_loss_bwd"""
     B = mask.shape[0]
-    n = probs.shape[0] // heads
-    Lc = probs.shape[-1]
-    assert probs.is_contiguous() and d_probs.is_contiguous() and d_probs.shape == probs.shape and n % B == 0
-    assert d_probs.dtype == torch.float32 and (loss is None or (loss.is_contiguous() and loss.numel() == n))
-    scratch = torch.empty((n, seg_mask.shape[1], 2), dtype=torch.float32, device=probs.device)
+    n, Lc = _ll_dims(probs, B, heads, loss, d_probs)
+    scratch = _ll_scratch(probs, n, seg_mask.shape[1], 2)
     L.check(L.load().udt_local_loss_bwd(_ptr(probs), _ptr(mask), _ptr(seg_mask), _ptr(gk9), _ptr(d_probs), _ptr(loss), _ptr(scratch), n, B,
                                         heads, size, Lc, seg_mask.shape[1], mask.shape[2], mask.shape[3], weight, _stream()),
             "udt_local_loss_bwd")
@@ -1178,11 +1190,8 @@ def local_loss_bwd_hw(probs: torch.Tensor, mask: torch.Tensor, seg_mask: torch.T
     """``local_loss_bwd`` on h x w maps: udt_local_loss_bwd_hw"""
     h, w = _check_map_hw(probs, hw, "local_loss_bwd_hw")
     B = mask.shape[0]
-    n = probs.shape[0] // heads
-    Lc = probs.shape[-1]
-    assert probs.is_contiguous() and d_probs.is_contiguous() and d_probs.shape == probs.shape and n % B == 0
-    assert d_probs.dtype == torch.float32 and (loss is None or (loss.is_contiguous() and loss.numel() == n))
-    scratch = torch.empty((n, seg_mask.shape[1], 2), dtype=torch.float32, device=probs.device)
+    n, Lc = _ll_dims(probs, B, heads, loss, d_probs)
+    scratch = _ll_scratch(probs, n, seg_mask.shape[1], 2)
     L.check(L.load().udt_local_loss_bwd_hw(_ptr(probs), _ptr(mask), _ptr(seg_mask), _ptr(gk9), _ptr(d_probs), _ptr(loss), _ptr(scratch), n,
                                            B, heads, h, w, Lc, seg_mask.shape[1], mask.shape[2], mask.shape[3], weight, _stream()),
             "udt_local_loss_bwd_hw")
@@ -1380,9 +1389,9 @@ def local_loss_seg_bwd(probs: torch.Tensor, seg: torch.Tensor, seg_mask: torch.T
                        loss: Optional[torch.Tensor], heads: int, size: int, weight: float) -> None:
     """FullLoss.get_local_loss per layer: d_probs += weight * d f / d probs, loss[b] += f_b (udt_local_loss_seg_bwd)"""
     B = seg.shape[0]
-    assert probs.is_contiguous() and d_probs.is_contiguous() and d_probs.shape == probs.shape and probs.shape[0] == B * heads
+    _ll_dims(probs, B, heads, loss, d_probs, tiled=False)
     assert seg.dtype == torch.float32 and seg.is_contiguous() and seg_mask.is_contiguous() and seg.shape[1] == seg_mask.shape[1]
-    scratch = torch.empty((B, seg.shape[1]), dtype=torch.float32, device=probs.device)
+    scratch = _ll_scratch(probs, B, seg.shape[1])
     L.check(L.load().udt_local_loss_seg_bwd(_ptr(probs), _ptr(seg), _ptr(seg_mask), _ptr(gk9), _ptr(d_probs), _ptr(loss), _ptr(scratch), B,
                                             heads, size, probs.shape[-1], seg.shape[1], seg.shape[2], seg.shape[3], weight, _stream()),
             "udt_local_loss_seg_bwd")
@@ -1393,9 +1402,9 @@ def local_loss_seg_bwd_hw(probs: torch.Tensor, seg: torch.Tensor, seg_mask: torc
     """``local_loss_seg_bwd`` on h x w maps: udt_local_loss_seg_bwd_hw"""
     h, w = _check_map_hw(probs, hw, "local_loss_seg_bwd_hw")
     B = seg.shape[0]
-    assert probs.is_contiguous() and d_probs.is_contiguous() and d_probs.shape == probs.shape and probs.shape[0] == B * heads
+    _ll_dims(probs, B, heads, loss, d_probs, tiled=False)
     assert seg.dtype == torch.float32 and seg.is_contiguous() and seg_mask.is_contiguous() and seg.shape[1] == seg_mask.shape[1]
-    scratch = torch.empty((B, seg.shape[1]), dtype=torch.float32, device=probs.device)
+    scratch = _ll_scratch(probs, B, seg.shape[1])
     L.check(L.load().udt_local_loss_seg_bwd_hw(_ptr(probs), _ptr(seg), _ptr(seg_mask), _ptr(gk9), _ptr(d_probs), _ptr(loss), _ptr(scratch),
                                                B, heads, h, w, probs.shape[-1], seg.shape[1], seg.shape[2], seg.shape[3], weight,
                                                _stream()), "udt_local_loss_seg_bwd_hw")

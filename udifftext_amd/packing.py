@@ -19,6 +19,14 @@ def pad_channels(c: int) -> int:
     return _round_up(c, KPAD)
 
 
+def conv_out_hw(H: int, W: int, ksize: int, stride: int, pad, upsample: bool = False) -> tuple:
+    """(Hout, Wout) of a convolution of an H x W map (read through a nearest x2 upsample if ``upsample``); pad = (top, left).
+    Host arithmetic, no launch: ops.conv2d and hipnn.Conv2d reach it as ``ops.conv_out_hw``"""
+    if upsample:
+        H, W = 2 * H, 2 * W
+    return (H + 2 * pad[0] - ksize) // stride + 1, (W + 2 * pad[1] - ksize) // stride + 1
+
+
 def pack_linear(w: torch.Tensor, n_pad_to: int = 4) -> torch.Tensor:
     """[N, K] fp32 -> bf16 [Npad, Kpad] (zero padded)."""
     N, K = w.shape

@@ -281,8 +281,7 @@ class Conv2d(_Packed):
         if colstats is None:
             colstats = self.emit_colstats
         if colstats:                                    # statistics are emitted where a consumer will use them
-            oh, ow = out_hw if out_hw is not None else ((x.shape[1] * (2 if upsample else 1) + 2 * pad[0] - self.kernel_size) // self.stride + 1,
-                                                        (x.shape[2] * (2 if upsample else 1) + 2 * pad[1] - self.kernel_size) // self.stride + 1)
+            oh, ow = out_hw if out_hw is not None else ops.conv_out_hw(x.shape[1], x.shape[2], self.kernel_size, self.stride, pad, upsample)
             colstats = want_stats(x.shape[0], oh * ow, w.shape[0])
         colstats = bool(colstats)
         kw = dict(ksize=self.kernel_size, stride=self.stride, pad=pad, upsample=upsample, out_hw=out_hw, residual=residual,
