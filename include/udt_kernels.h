@@ -509,6 +509,27 @@ int udt_local_loss_tiled(const float* probs, const float* mask, const float* seg
 int udt_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, void* dq, void* dk, void* dv,
                  float* lse_ws, float* dsum_ws, int32_t batch, int32_t heads, int32_t n, int32_t ldq, int32_t ldo, int32_t ldd,
                  float scale, void* stream);
+/* flash-attention backward for ONE head of 512 dims, self-attention (the AutoencoderKL mid-block attention under autograd; forward:
+ * udt_attn512_fwd; csrc/attn512_bwd.hip).  Rows are (b, tok): row strides ld* and batch strides *_bstride in elements, as the forward
+ * takes them; q, k, v may be column ranges of one projection, o / d_o [batch * n, >= 512], dq, dk, dv column ranges of one matrix (row
+ * stride ldd, batch stride d_bstride).  lse_ws / dsum_ws: fp32 [batch * n] scratch each (log-sum-exp of every score row and
+ * rowsum(dO o O): written by the first launch, read by the second).  Two launches, no [n, n] tensor, no atomics, fixed summation
+ * order (bit-identical runs).  Any n >= 1: rows past n are masked and never read.  Every pointer 16-byte aligned, every ld and batch
+ * stride a multiple of 8 (refused on the host otherwise, with n < 1 and null pointers).  fp32 scores, statistics and accumulators;
+ * P and dS rounded to bf16 once for the second products; results rounded to bf16 once. */
+int udt_attn512_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, void* dq, void* dk, void* dv,
+                    float* lse_ws, float* dsum_ws, int32_t batch, int32_t n, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
+                    int32_t lddo, int32_t ldd, int64_t q_bstride, int64_t k_bstride, int64_t v_bstride, int64_t o_bstride,
+                    int64_t do_bstride, int64_t d_bstride, float scale, void* stream);
+/* the denoiser's output for the OCR term of the training loss (reference loss.py:178-190 takes model_output = D):
+ * out[b, c, pix] = c_skip[b] * noised[b, c, pix] + c_out[b] * f[b, pix, c], c < 4; f fp32 NHWC [B, hw, ld] (16-byte aligned, ld % 4
+ * == 0), noised / out fp32 NCHW [B, 4, hw], c_skip / c_out fp32 [B] on the device */
+int udt_denoised_f32(const float* f, const float* noised, const float* c_skip, const float* c_out, float* out, int32_t B, int32_t hw,
+                     int32_t ld, void* stream);
+/* seed[b, pix, c] += c_out[b] * g[b, c, pix], c < 4: the OCR term's gradient with respect to D (g fp32 NCHW [B, 4, hw]) added into the
+ * reverse pass's bf16 NHWC loss seed [B, hw, cpad] (8-byte aligned, cpad % 4 == 0; channels 4 .. cpad - 1 untouched); fp32
+ * arithmetic, one rounding */
+int udt_seed_add_bf16(void* seed, const float* g, const float* c_out, int32_t B, int32_t hw, int32_t cpad, void* stream);
 /* text cross-attention backward (reference attention.py:140-175 CrossAttention under autograd; context constant): probs fp32
  * [batch * heads, nq, L] as udt_xattn_fwd wrote them, d_probs (optional) the loss gradient with respect to them, d_o (optional) bf16
  * [batch * nq, ldo] the gradient of the attention output -> dq bf16 [batch * nq, lddq] (head h at columns h * 64); L <= 16, and

@@ -140,6 +140,10 @@ SYMBOLS = {
     "udt_local_loss": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "udt_local_loss_tiled": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "udt_attn_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "udt_attn512_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64,
+                                  _i64, _i64, _i64, _i64, _i64, _f32, _vp]),
+    "udt_denoised_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _vp]),
+    "udt_seed_add_bf16": (C.c_int, [_vp, _fp, _fp, _i32, _i32, _i32, _vp]),
     "udt_xattn_bwd": (C.c_int, [_vp, _vp, _fp, _fp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "udt_local_loss_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "udt_local_loss_bwd_hw": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32,

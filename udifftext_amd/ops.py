@@ -1155,6 +1155,55 @@ def attention_bwd(qkv: torch.Tensor, o: torch.Tensor, d_o: torch.Tensor, heads: 
     return dqkv
 
 
+def attention_d512_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, d_o: torch.Tensor, scale: float,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """flash-attention backward of ``attention_d512(q, k, v, scale)`` (self-attention): q, k, v [B, N, 512] row views (e.g. the column
+    ranges of one q|k|v projection), o / d_o bf16 [B, N, 512] row views -> d(q|k|v) bf16 [B, N, 1536] (``out``: a [B, N, >= 1536] row
+    view to write into; its first 1536 columns are returned).  udt_attn512_bwd: two launches, deterministic, no [N, N] tensor."""
+    for t in (q, k, v, o, d_o):
+        _bf16(t)
+        assert t.dim() == 3 and t.shape[2] == 512 and t.stride(2) == 1 and t.shape[:2] == q.shape[:2]
+    B, N = q.shape[0], q.shape[1]
+    if out is None:
+        out = torch.empty((B, N, 1536), dtype=torch.bfloat16, device=q.device)
+    _bf16(out)
+    assert out.shape[:2] == (B, N) and out.shape[2] >= 1536 and out.stride(2) == 1
+    _drop_sidecars(out)
+    ws = torch.empty((2, B * N), dtype=torch.float32, device=q.device)
+    es = out.element_size()
+    L.check(L.load().udt_attn512_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(d_o), out.data_ptr(), out.data_ptr() + 512 * es,
+                                     out.data_ptr() + 1024 * es, ws[0].data_ptr(), ws[1].data_ptr(), B, N, q.stride(1), k.stride(1),
+                                     v.stride(1), o.stride(1), d_o.stride(1), out.stride(1), q.stride(0), k.stride(0), v.stride(0),
+                                     o.stride(0), d_o.stride(0), out.stride(0), scale, _stream()), "udt_attn512_bwd")
+    return out[..., :1536]
+
+
+def denoised(f: torch.Tensor, noised: torch.Tensor, c_skip: torch.Tensor, c_out: torch.Tensor) -> torch.Tensor:
+    """D = c_skip_b * noised + c_out_b * F, fp32 NCHW [B, 4, h, w]: f fp32 NHWC [B, h, w, ld] (the UNet head's output), noised fp32
+    NCHW, c_skip / c_out fp32 [B] on the device (udt_denoised_f32, one launch)"""
+    B, h, w, ld = f.shape
+    assert f.dtype == torch.float32 and f.is_contiguous() and noised.dtype == torch.float32 and noised.is_contiguous()
+    assert noised.shape == (B, 4, h, w)
+    for t in (c_skip, c_out):
+        assert t.dtype == torch.float32 and t.numel() == B and t.is_contiguous() and t.device == f.device
+    out = torch.empty_like(noised)
+    L.check(L.load().udt_denoised_f32(_ptr(f), _ptr(noised), _ptr(c_skip), _ptr(c_out), _ptr(out), B, h * w, ld, _stream()),
+            "udt_denoised_f32")
+    return out
+
+
+def seed_add_(seed: torch.Tensor, g: torch.Tensor, c_out: torch.Tensor) -> torch.Tensor:
+    """seed[b, y, x, c] += c_out_b * g[b, c, y, x] for the 4 latent channels, in place: seed bf16 NHWC [B, h, w, cpad] (the reverse
+    pass's loss seed), g fp32 NCHW [B, 4, h, w], c_out fp32 [B] on the device (udt_seed_add_bf16, one launch)"""
+    _bf16(seed)
+    B, h, w, cpad = seed.shape
+    assert seed.is_contiguous() and g.dtype == torch.float32 and g.is_contiguous() and g.shape == (B, 4, h, w)
+    assert c_out.dtype == torch.float32 and c_out.numel() == B and c_out.is_contiguous() and c_out.device == seed.device
+    _drop_sidecars(seed)
+    L.check(L.load().udt_seed_add_bf16(_ptr(seed), _ptr(g), _ptr(c_out), B, h * w, cpad, _stream()), "udt_seed_add_bf16")
+    return seed
+
+
 def xattention_bwd(k: torch.Tensor, v: torch.Tensor, probs: torch.Tensor, d_probs: Optional[torch.Tensor],
                    d_o: Optional[torch.Tensor], heads: int, scale: float) -> torch.Tensor:
     """dq of the text cross-attention: k, v row views [B, L, *] (as ``xattention``), probs / d_probs fp32 [B * heads, Nq, L],

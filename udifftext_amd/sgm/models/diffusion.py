@@ -124,8 +124,20 @@ class DiffusionEngine(nn.Module):
         [B, 4, h, w]; batch: ``label`` / ``mask`` / ``masked`` for the conditioner (its ucg draw included) plus ``seg`` / ``seg_mask``"""
         from udifftext_amd import training
         cond = self.conditioner(batch)
-        loss_dict, _ = training.training_loss_and_grads(self, x, cond, batch["seg"], batch["seg_mask"], want_grads=False)
+        loss_dict, _ = training.training_loss_and_grads(self, x, cond, batch["seg"], batch["seg_mask"], want_grads=False,
+                                                        **self._ocr_inputs(batch))
         return loss_dict["loss/full_loss"], loss_dict
+
+    def _ocr_inputs(self, batch) -> dict:
+        """what the OCR term reads besides the latents (reference loss.py:165-166: batch["r_bbox"], batch["label"], the first stage
+        and its scale factor); empty when the term is off, so that the call is what it was"""
+        if not getattr(self.loss_fn, "ocr_enabled", False):
+            return {}
+        r_bbox = batch.get("r_bbox")
+        if isinstance(r_bbox, torch.Tensor):
+            r_bbox = r_bbox.cpu()                                        # (the boxes are read on the host: they size the crops)
+        return dict(r_bbox=r_bbox, label=batch.get("label"), first_stage_model=self.first_stage_model,
+                    scaler=self.scale_factor)
 
     def shared_step(self, batch, bucket=None):
         """reference :144-149 (latents from the first stage, then the loss) — with the gradients of the trained parameters (added
@@ -133,7 +145,7 @@ class DiffusionEngine(nn.Module):
         from udifftext_amd import training
         x = self.encode_first_stage(self.get_input(batch))
         cond = self.conditioner(batch)
-        return training.training_loss_and_grads(self, x, cond, batch["seg"], batch["seg_mask"], bucket=bucket)
+        return training.training_loss_and_grads(self, x, cond, batch["seg"], batch["seg_mask"], bucket=bucket, **self._ocr_inputs(batch))
 
     def _build_ema(self) -> None:
         """reference :75-78, for the tensors opt_keys trains (LitEma moves no others, sgm/modules/ema.py:46-54); without opt_keys

@@ -3,7 +3,8 @@
 Only what inference touches is implemented (reference sgm/modules/diffusionmodules/loss.py):
 ``FullLoss.__init__`` (:73-101, builds the sigma sampler and the ``g_kernel`` buffer — a state-dict entry),
 ``get_gaussian_kernel`` (:103-129) and ``get_min_local_loss`` (:192-235, scores how well the t_attn maps of the
-characters land inside the mask; used by the initial-noise search).  Training losses are out of scope.
+characters land inside the mask; used by the initial-noise search), and the OCR term ``get_ocr_loss`` (:178-190) with its
+gradient.  ``FullLoss.__call__`` itself is udifftext_amd.training.training_loss_and_grads.
 """
 from __future__ import annotations
 
@@ -54,8 +55,8 @@ class FullLoss(StandardDiffusionLoss):
         GPU (the decoder's output as it is, in [-1, 1]: the reference does not remap it), r_bbox: per image (top, bottom, left, right) on
         the host, label: B strings -> ``self.predictor.calc_loss_boxes`` on the boxes (i, *r_bbox[i]): (ocr loss fp32 [B], its gradient
         with respect to ``decoded`` fp32 [B, 3, H, W], or None without ``want_grad``).
-        The other half — ``model_output / scaler`` and the VAE decoder's backward-data pass, which carries this gradient to the UNet's
-        output — is not built: ``training.check_trainable`` still refuses ``ocr_enabled``.
+        The other half — ``model_output / scaler`` and the VAE decoder's reverse pass, which carries this gradient to the UNet's
+        output — is ``get_ocr_loss``.
         ValueError when there is no predictor (``ocr_enabled`` was false at construction)."""
         predictor = getattr(self, "predictor", None)
         if predictor is None:
@@ -65,6 +66,25 @@ class FullLoss(StandardDiffusionLoss):
         rows = torch.as_tensor(r_bbox).reshape(-1, 4).tolist()
         boxes = [[i] + list(bb) for i, bb in enumerate(rows)]
         return predictor.calc_loss_boxes(decoded, boxes, label, weight=weight, want_grad=want_grad)
+
+    def get_ocr_loss(self, model_output, r_bbox, label, first_stage_model, scaler, want_grad: bool = True, weight=None):
+        """reference loss.py:178-190, its arguments in its order: ``model_output / scaler`` -> ``first_stage_model.decode`` -> the crop
+        of every image's box -> ``predictor.calc_loss``.  model_output fp32 [B, 4, h, w] on the GPU (the denoiser's output D).
+        -> (ocr loss fp32 [B], d_model_output fp32 [B, 4, h, w] or None without ``want_grad``):
+        d_model_output = (1 / scaler) * decoder_vjp(d_decoded), d_decoded from ``get_ocr_loss_decoded`` (``weight``: the upstream
+        cotangent of each row's loss, passed through to it).  The decoder runs on a tape (vae_backward.decode_tape) only when the
+        gradient is wanted.  ``lambda_ocr_loss * mean`` is the caller's (training.training_loss_and_grads).
+        ValueError when there is no predictor."""
+        if getattr(self, "predictor", None) is None:
+            raise ValueError("get_ocr_loss needs the OCR predictor: construct FullLoss with ocr_enabled=True and a predictor_config")
+        from udifftext_amd import vae_backward
+        z = (model_output.float() * (1.0 / float(scaler))).contiguous()
+        if not want_grad:
+            loss, _ = self.get_ocr_loss_decoded(first_stage_model.decode(z), r_bbox, label, weight=weight, want_grad=False)
+            return loss, None
+        frames, bwd = vae_backward.decode_tape(first_stage_model, z)
+        loss, d_frames = self.get_ocr_loss_decoded(frames, r_bbox, label, weight=weight, want_grad=True)
+        return loss, bwd(d_frames) / float(scaler)
 
     def scores_map(self, hw) -> bool:
         """a t_attn layer is scored when min(h, w) >= min_attn_size: the reference's ``size >= min_attn_size`` for h == w (it

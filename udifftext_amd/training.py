@@ -11,8 +11,9 @@ back-propagate to the parameters whose names contain an ``opt_keys`` entry (conf
 Here: the tape-mode forward and the written-out reverse pass of ``udifftext_amd.backward`` (dX through every layer, dW only where
 the reference trains), the two loss seeds and the optimiser update as HIP kernels (csrc/backward.hip), one flat fp32 bucket per step
 through ``torch.distributed`` (RCCL on the GPUs: reduce-scatter + all-gather, the bandwidth-optimal form on the xGMI mesh; gloo's
-all_reduce in the CPU tests).  The OCR / style losses (ocr_enabled / style_enabled: False in every shipped config) and the
-Lightning loop itself stay out of scope.
+all_reduce in the CPU tests).  The OCR loss (ocr_enabled; False in every shipped config) runs through the VAE decoder's reverse pass
+(udifftext_amd.vae_backward).  The style loss (style_enabled) cannot be built — the reference calls
+``get_style_local_loss``, which it never defines — and the Lightning loop itself stays out of scope.
 
 Gradient accumulation and EMA (configs/train.yaml:21 ``accumulate_grad_batches``; diffusion.py:75-78,178-195 with sgm/modules/ema.py)
 run on the fused route: the trained tensors' gradients live in ONE persistent flat bucket (``GradBucket``), the reverse pass ADDS into
@@ -47,8 +48,11 @@ def check_trainable(engine) -> None:
         raise NotImplementedError(f"loss type {loss_fn.type!r}: the loss seed kernels implement the l2 loss")
     if loss_fn.offset_noise_level > 0:
         raise NotImplementedError("offset_noise_level > 0 is not implemented")
-    if loss_fn.style_enabled or loss_fn.ocr_enabled:
-        raise NotImplementedError("the style and OCR losses (style_enabled / ocr_enabled) are not implemented")
+    if loss_fn.style_enabled:
+        raise NotImplementedError("the style loss (style_enabled) is not implemented: the reference's FullLoss.__call__ calls "
+                                  "get_style_local_loss, which the reference has no definition of")
+    if loss_fn.ocr_enabled and getattr(loss_fn, "predictor", None) is None:
+        raise NotImplementedError("ocr_enabled without an OCR predictor: construct FullLoss with a predictor_config")
     if type(loss_fn.sigma_sampler) not in (DiscreteSampling, EDMSampling):
         raise NotImplementedError(f"sigma sampler {type(loss_fn.sigma_sampler).__name__}: DiscreteSampling and EDMSampling are implemented")
     conditioner = getattr(engine, "conditioner", None)
@@ -67,7 +71,8 @@ def _eps_path(engine) -> bool:
 
 def training_loss_and_grads(engine, z: torch.Tensor, cond: dict, seg: torch.Tensor, seg_mask: torch.Tensor,
                             sigma_idx: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-                            want_grads: bool = True, sigma: Optional[torch.Tensor] = None, bucket: Optional["GradBucket"] = None):
+                            want_grads: bool = True, sigma: Optional[torch.Tensor] = None, bucket: Optional["GradBucket"] = None,
+                            r_bbox=None, label=None, first_stage_model=None, scaler: Optional[float] = None):
     """FullLoss.__call__ on latents z fp32 [B, 4, h, w] with conditioning ``cond`` ({"concat": [B, 5, h, w], "t_crossattn":
     [B, L, Dc]}), character segment maps seg fp32 [B, seg_l, Hs, Ws] and seg_mask [B, seg_l].
     sigma_idx int64 [B] (default: DiscreteSampling's torch.randint draw; EDMSampling: one CPU torch.randn((B,))), or ``sigma``
@@ -75,8 +80,15 @@ def training_loss_and_grads(engine, z: torch.Tensor, cond: dict, seg: torch.Tens
     the step's random draws.  Returns (loss_dict, grads): loss_dict as the reference's (``loss/diff_loss``,
     ``loss/local_loss``, ``loss/full_loss``: 0-dim fp32 tensors), grads = {state-dict name: fp32 gradient of loss/full_loss} for the
     t_attn / t_norm parameters (None when want_grads is False).  ``bucket``: a GradBucket the gradients are ADDED to instead (one
-    micro-batch of an accumulation window); grads is then the bucket."""
+    micro-batch of an accumulation window); grads is then the bucket.
+    With ``loss_fn.ocr_enabled`` (reference loss.py:159-166): r_bbox (per image (top, bottom, left, right), on the host) and label (B
+    strings) are required; first_stage_model / scaler default to the engine's.  The denoiser's output D = c_skip noised + c_out F
+    is materialised in fp32, ``loss_fn.get_ocr_loss`` runs with weight lambda_ocr_loss / B, and c_out[b] * d_D is added into the
+    loss seed before the reverse pass; the loss dict gains ``loss/ocr_loss`` and full_loss lambda_ocr_loss * ocr_loss."""
     loss_fn = engine.loss_fn
+    ocr = bool(loss_fn.ocr_enabled)
+    if ocr and (r_bbox is None or label is None):
+        raise ValueError("ocr_enabled: training_loss_and_grads needs r_bbox and label (batch['r_bbox'], batch['label'])")
     B = z.shape[0]
     dev = z.device
     tape, noised, sigma = training_tape(engine, z, cond, sigma_idx, noise, sigma)
@@ -98,6 +110,21 @@ def training_loss_and_grads(engine, z: torch.Tensor, cond: dict, seg: torch.Tens
     diff = loss_diff.mean()
     local = loss_local.mean() / max(len(used), 1)
     loss_dict = {"loss/diff_loss": diff, "loss/local_loss": local, "loss/full_loss": diff + lam * local}
+    if ocr:
+        lam_ocr = float(loss_fn.lambda_ocr_loss)
+        if tape.precond is None:                                         # eps path: D = noised - sigma eps
+            c_skip, c_out = torch.ones_like(sigma), -sigma
+        else:
+            c_skip, c_out = tape.precond[0], tape.precond[1]
+        den = ops.denoised(tape.eps, noised, c_skip, c_out)
+        fsm = first_stage_model if first_stage_model is not None else engine.first_stage_model
+        sc = float(scaler if scaler is not None else engine.scale_factor)
+        loss_ocr, d_den = loss_fn.get_ocr_loss(den, r_bbox, label, fsm, sc, want_grad=want_grads, weight=lam_ocr / B)
+        if d_den is not None:
+            ops.seed_add_(d_eps, d_den.contiguous(), c_out.contiguous())
+        ocr_mean = loss_ocr.mean()
+        loss_dict["loss/ocr_loss"] = ocr_mean
+        loss_dict["loss/full_loss"] = loss_dict["loss/full_loss"] + lam_ocr * ocr_mean
     if not want_grads:
         return loss_dict, None
     if bucket is not None:
