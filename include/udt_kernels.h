@@ -44,6 +44,8 @@
  *   udt_mask_downsample SpatialRescaler (bilinear x0.125)  sgm/modules/encoders/modules.py:843-857
  *   udt_crop_resize_aa_f32  the OCR scorer's input side, every box of every image in one launch: the crop results[i, :, t:b, l:r]
  *                       (test.py:81) + Resize(BICUBIC, antialias=True) + Normalize(0.5, 0.5)  sgm/modules/predictors/model.py:24-29
+ *   udt_tattn_fused_maps / udt_resize_bilinear_f32   the per-character attention maps (cfgs.detailed): head mean of the t_attn
+ *                       probabilities out of the fused kernel, openaimodel.py:559-591, sampling.py:344-346,380; cv2.resize, demo.py:109
  *   udt_local_loss_maps head-mean + 3x3 blur + masked max of t_attn maps  sgm/modules/diffusionmodules/loss.py:192-235
  *   the reverse pass (round 6; torch.autograd under attend_and_excite, sgm/modules/diffusionmodules/sampling.py:233-252, and under
  *   DiffusionEngine.training_step, sgm/models/diffusion.py:138-172 with loss.py:131-176,237-286):
@@ -345,6 +347,26 @@ int32_t udt_tattn_rowstat_parts(int32_t B, int32_t n_tok, int32_t C);
 int udt_tattn_fused_q8(const void* x, void* out, const void* A, const float* sc, const void* BmT, const float* bias,
                        int32_t B, int32_t n_tok, int32_t C, int32_t heads, int32_t zero_samples, float eps, void* q8_out,
                        void* q8_scale, float* rowstat_out, void* stream);
+/* udt_tattn_fused (q8_out == NULL) or udt_tattn_fused_q8 (q8_out != NULL: q8_scale and rowstat_out as there) that ALSO writes the
+ * per-character attention maps of the launch, the reference's head mean of the text-attention probabilities (cfgs.detailed:
+ * sgm/modules/diffusionmodules/openaimodel.py:559-591, sampling.py:344-346,380):
+ *   maps[b - map_from][l][t]  (=  or  +=)  weight * (1 / heads) * sum_h P[b, t, h, l]      b >= map_from, l < L, t < n_tok
+ * maps fp32 [B - map_from, L, n_tok], token fastest (the reference's permute(0, 2, 1).reshape(b, l, h, w), row-major over the h x w
+ * tokens).  Domain: that of the plain entry point, plus 1 <= L <= 12 = the context length the tables were prepared for (the 16 - L
+ * padded columns of a head are never read into a map) and zero_samples <= map_from <= B: samples below map_from (the unconditional
+ * half of a CFG pair, zero-context rows) have no plane.  accumulate == 0 stores, != 0 adds to what maps holds: the selected layers of
+ * one UNet call average into one buffer in launch order (weight = 1 / n_layers; the first stores, the rest add).
+ * out, q8_out, q8_scale and rowstat_out are bit-identical to the plain entry point's on the same operands.
+ * ROUNDING (maps): each probability is the bf16 value the output GEMM of the kernel reads (the fp32 softmax rounded to bf16 once,
+ * to nearest even); the heads are added in ascending order in fp32; the sum is multiplied by fp32(weight / heads) and rounded;
+ * accumulate adds that to the stored fp32 value and rounds once more.  One workgroup per token tile writes and nothing is atomic:
+ * bit-identical from run to run.
+ * UDT_ERR_BAD_ARG: a null maps (and what the plain entry point answers it for); UDT_ERR_BAD_SHAPE: L < 1, L > 12, map_from outside
+ * [zero_samples, B] (and what the plain entry point answers it for).  Nothing is launched in either case. */
+int udt_tattn_fused_maps(const void* x, void* out, const void* A, const float* sc, const void* BmT, const float* bias,
+                         int32_t B, int32_t n_tok, int32_t C, int32_t heads, int32_t zero_samples, float eps, float* maps,
+                         int32_t L, int32_t map_from, float weight, int32_t accumulate, void* q8_out, void* q8_scale,
+                         float* rowstat_out, void* stream);
 
 /* Row softmax of a bf16 [rows, cols] matrix in place (ld elements between rows), fp32 math. */
 int udt_softmax_rows(void* x, int64_t rows, int32_t cols, int32_t ld, void* stream);
@@ -712,6 +734,16 @@ int udt_crop_resize_aa_f32(const float* img, const int32_t* boxes, float* out, i
  * UDT_ERR_BAD_ARG: a null pointer; UDT_ERR_BAD_SHAPE: a dimension < 1, H, B * C or N > 65535.  Nothing is launched in either case. */
 int udt_crop_resize_aa_bwd_f32(const float* d_out, const int32_t* boxes, float* d_img, int B, int C, int H, int W, int N, int out_h,
                                int out_w, float mul, void* stream);
+/* Bilinear resize of fp32 planes in one launch (the character maps at image size: demo.py:109 cv2.resize(seg_map, (W, H)), which is
+ * F.interpolate(mode="bilinear", align_corners=False)): in fp32 [planes, h, w], out fp32 [planes, H, W], contiguous.  Half-pixel
+ * centres with edge clamp; down-scaling is plain bilinear, no antialiasing.  Along an axis of n_in input and n_out output samples,
+ * output i reads the source coordinate max(0, (2 i + 1) n_in - n_out) / (2 n_out), held as that integer fraction: taps
+ * i0 = min(floor, n_in - 1) and i1 = min(i0 + 1, n_in - 1) are exact, the weights w1 = frac and w0 = 1 - frac are each the exact
+ * rational rounded to fp32 once.
+ * ROUNDING: out = fma(wy1, bot, wy0 * top) with top = fma(wx1, in[i0y][i1x], wx0 * in[i0y][i0x]) and bot likewise on row i1y, fp32.
+ * Any H, W >= 1.  Bit-identical from run to run.
+ * UDT_ERR_BAD_ARG: a null pointer; UDT_ERR_BAD_SHAPE: a dimension < 1, planes * H * W >= 2^40.  Nothing is launched in either case. */
+int udt_resize_bilinear_f32(const float* in, float* out, int64_t planes, int32_t h, int32_t w, int32_t H, int32_t W, void* stream);
 /* Backward of udt_mattn_fwd: same operands and layout (q, k, v bf16 row views with their ld and batch strides, optional fp32 additive
  * mask [nq, ldmask], optional uint8 kpm [batch, lk]) plus
  *   d_o : bf16 rows (b, i) at d_o + b*do_bstride + i*lddo + h*head_dim, the cotangent of o

@@ -231,7 +231,54 @@ __global__ void __launch_bounds__(RB_COLS) crop_resize_aa_bwd_kernel(const float
   if (x < W) dst[x] = inside ? mul * acc : 0.f;
 }
 
+// ---- bilinear resize of fp32 planes (the character maps at image size: demo.py:109 cv2.resize, F.interpolate(mode="bilinear",
+// align_corners=False)).  Half-pixel centres, edge clamp: output i reads source coordinate ((2 i + 1) n_in - n_out) / (2 n_out),
+// clamped below at 0 — kept as that integer fraction, so the two taps are exact and the weights are the fraction rounded to fp32 once.
+struct BlTap { int i0, i1; float w0, w1; };
+UDT_DEVINL BlTap bl_tap(int i, int n_in, int n_out) {
+  const long long den = 2LL * n_out;
+  long long num = (2LL * i + 1) * n_in - n_out;
+  if (num < 0) num = 0;
+  const long long q = num / den, r = num - q * den;
+  BlTap t;
+  t.i0 = (int)min(q, (long long)(n_in - 1));
+  t.i1 = min(t.i0 + 1, n_in - 1);
+  t.w1 = (float)((double)r / (double)den);
+  t.w0 = (float)((double)(den - r) / (double)den);
+  return t;
+}
+// one thread per output element, x fastest
+__global__ void __launch_bounds__(256) resize_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, long long total,
+                                                              int h, int w, int H, int W) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int ox = (int)(idx % W);
+  const long long rest = idx / W;
+  const int oy = (int)(rest % H);
+  const long long plane = rest / H;
+  const BlTap ty = bl_tap(oy, h, H), tx = bl_tap(ox, w, W);
+  const float* r0 = in + (plane * h + ty.i0) * (long long)w;
+  const float* r1 = in + (plane * h + ty.i1) * (long long)w;
+  const float top = __builtin_fmaf(tx.w1, r0[tx.i1], tx.w0 * r0[tx.i0]);
+  const float bot = __builtin_fmaf(tx.w1, r1[tx.i1], tx.w0 * r1[tx.i0]);
+  out[idx] = __builtin_fmaf(ty.w1, bot, ty.w0 * top);
+}
+
 }  // namespace
+
+extern "C" int udt_resize_bilinear_f32(const float* in, float* out, int64_t planes, int32_t h, int32_t w, int32_t H, int32_t W,
+                                       void* stream) {
+  if (!in || !out) return UDT_ERR_BAD_ARG;
+  if (planes <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return UDT_ERR_BAD_SHAPE;
+  if (planes > (1LL << 40) / ((long long)H * W)) return UDT_ERR_BAD_SHAPE;                // (grid limit: 2^31 workgroups of 256)
+  const long long total = (long long)planes * H * W;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  UdtProfScope prof(5, s);
+  hipLaunchKernelGGL(resize_bilinear_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, total, (int)h, (int)w,
+                     (int)H, (int)W);
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}
 
 extern "C" int udt_crop_resize_aa_bwd_f32(const float* d_out, const int32_t* boxes, float* d_img, int B, int C, int H, int W, int N,
                                           int out_h, int out_w, float mul, void* stream) {

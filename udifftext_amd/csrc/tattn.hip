@@ -49,6 +49,10 @@ struct TattnParams {
   uint8_t* q8_out;         // [M, C] e4m3
   uint32_t* q8_scale;      // [C / 128][M]
   float* rowstat_out;      // [nsplit][M][2]
+  // MAPS instances (udt_tattn_fused_maps): the head mean of P per (sample >= map_from, context token, token)
+  float* maps;             // [B - map_from][map_L][n_tok] fp32
+  int heads, map_L, map_from, map_acc;
+  float map_scale;         // weight / heads
 };
 
 UDT_DEVINL f32x16 zero16() {
@@ -59,7 +63,7 @@ UDT_DEVINL f32x16 zero16() {
 }
 
 // TT tokens per workgroup (64, or 32 for C = 1280 so that the x tile fits in LDS), 8 waves; NKT = C / 64, NKS = hp / 16
-template <int TT, int NKT, int NKS, bool Q8 = false>
+template <int TT, int NKT, int NKS, bool Q8 = false, bool MAPS = false>
 __global__ void __launch_bounds__(TA_THREADS) tattn_fused_kernel(const TattnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int C = NKT * 64, hp = NKS * 16;
@@ -265,6 +269,26 @@ __global__ void __launch_bounds__(TA_THREADS) tattn_fused_kernel(const TattnPara
   }
   __syncthreads();
 
+  // ---- MAPS: maps[b - map_from][l][token] (= or +=) (weight / heads) * sum_h P[token][16 h + l], from the bf16 P tile every wave has
+  // just completed (the heads of a token lie in different waves' score tiles: the sum has to cross them, and LDS is where they meet).
+  // One workgroup per token tile writes (channel split 0); a thread owns one (l, token), tokens fastest: 4-byte stores, 128 or 256
+  // contiguous bytes per l.  Heads are added in ascending order in fp32: no atomics, the same bits every run.
+  if constexpr (MAPS) {
+    if (blockIdx.y == 0 && b >= p.map_from) {
+#pragma clang fp contract(off)      // (sum * scale is rounded before the accumulate form adds it: the store and add forms agree on it)
+      float* const mb = p.maps + (long long)(b - p.map_from) * p.map_L * p.n_tok + (tok0 - (long long)b * p.n_tok);
+      for (int i = tid; i < TT * p.map_L; i += TA_THREADS) {
+        const int l = i / TT, row = i - l * TT;
+        const char* pr = pl + (size_t)row * prs + l * 2;
+        float s = 0.f;
+        for (int h = 0; h < p.heads; ++h) s += bf16_bits_to_f32(*reinterpret_cast<const uint16_t*>(pr + h * 32));
+        s *= p.map_scale;
+        float* dst = mb + (long long)l * p.n_tok + row;
+        if (tok0 + row < p.M) *dst = p.map_acc ? *dst + s : s;
+      }
+    }
+  }
+
   // ---- out^T = Bm^T P^T  (D rows = channels, D cols = tokens) + bias + residual -> store ---------------------------------
   const uint16_t* Bb = p.BmT + (long long)b * C * hp;
   const int tiles2 = (ct_hi - ct_lo) * (TT / 32);
@@ -432,11 +456,15 @@ int tattn_nsplit(int M, int TT) {
 }
 
 int tattn_launch(const void* x, void* out, const void* A, const float* sc, const void* BmT, const float* bias, int32_t B, int32_t n_tok,
-                 int32_t C, int32_t heads, int32_t zero_samples, float eps, void* q8_out, void* q8_scale, float* rowstat_out, void* stream) {
+                 int32_t C, int32_t heads, int32_t zero_samples, float eps, void* q8_out, void* q8_scale, float* rowstat_out, void* stream,
+                 bool with_maps = false, float* maps = nullptr, int32_t L = 0, int32_t map_from = 0, float weight = 0.f,
+                 int32_t accumulate = 0) {
+  if (with_maps && !maps) return UDT_ERR_BAD_ARG;
   if (!x || !out || !bias || (zero_samples < B && (!A || !sc || !BmT))) return UDT_ERR_BAD_ARG;
   if (B <= 0 || n_tok <= 0 || heads <= 0 || C != heads * 64 || C > 1280 || zero_samples < 0 || zero_samples > B) return UDT_ERR_BAD_SHAPE;
   const int TT = tattn_tt(C);
   if (n_tok % TT != 0) return UDT_ERR_BAD_SHAPE;             // a token tile lies in one sample
+  if (with_maps && (L < 1 || L > 12 || map_from < zero_samples || map_from > B)) return UDT_ERR_BAD_SHAPE;
   const bool q8 = q8_out != nullptr;
   if (q8 && (!q8_scale || !rowstat_out || C % 128 != 0)) return UDT_ERR_BAD_ARG;
   TattnParams p;
@@ -446,25 +474,29 @@ int tattn_launch(const void* x, void* out, const void* A, const float* sc, const
   if (!p.zero) return UDT_ERR_HIP;
   p.M = B * n_tok; p.C = C; p.hp = udt_tattn_hp(heads); p.n_tok = n_tok; p.zero_samples = zero_samples; p.eps = eps;
   p.q8_out = reinterpret_cast<uint8_t*>(q8_out); p.q8_scale = reinterpret_cast<uint32_t*>(q8_scale); p.rowstat_out = rowstat_out;
+  p.maps = maps; p.heads = heads; p.map_L = L; p.map_from = map_from; p.map_acc = accumulate != 0; p.map_scale = weight / (float)heads;
   const size_t smem = (size_t)TT * C * 2 + (size_t)TT * 2 * sizeof(float) + (size_t)TT * (p.hp * 2 + 16) + (q8 ? (size_t)TT * (C / 32) * 8 : 0);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   UdtProfScope prof(3, s);
   if (prof.rec) {
     char tag[96];
-    snprintf(tag, sizeof(tag), "tattn_fused%s B=%d n=%d C=%d zero=%d", q8 ? "+q8" : "", B, n_tok, C, zero_samples);
+    snprintf(tag, sizeof(tag), "tattn_fused%s%s B=%d n=%d C=%d zero=%d", q8 ? "+q8" : "", with_maps ? "+maps" : "", B, n_tok, C, zero_samples);
     udt_prof_tag(prof.rec, tag);
   }
-  static bool attr_done[5] = {false, false, false, false, false};   // (max dynamic LDS; set once per process — one device per process)
+  static bool attr_done[10] = {};   // (max dynamic LDS; set once per process — one device per process)
   const unsigned grid = (unsigned)(p.M / TT);
   p.nsplit = tattn_nsplit(p.M, TT);
   // instances: the UNet's three widths (C = 320 / 640 / 1280 with 5 / 10 / 20 heads: hp = 80 -> padded 96, 160, 320); the MX8-emitting
   // form for the two widths whose linears run on e4m3 operands in config #5
   const void* fn = nullptr;
   int which = -1;
-  if (C == 320 && p.hp == 96 && !q8) { fn = reinterpret_cast<const void*>(tattn_fused_kernel<64, 5, 6>); which = 0; }
-  else if (C == 640 && p.hp == 160) { fn = q8 ? reinterpret_cast<const void*>(tattn_fused_kernel<32, 10, 10, true>) : reinterpret_cast<const void*>(tattn_fused_kernel<32, 10, 10>); which = q8 ? 3 : 1; }
-  else if (C == 1280 && p.hp == 320) { fn = q8 ? reinterpret_cast<const void*>(tattn_fused_kernel<32, 20, 20, true>) : reinterpret_cast<const void*>(tattn_fused_kernel<32, 20, 20>); which = q8 ? 4 : 2; }
+#define UDT_TATTN_FN(...) (with_maps ? reinterpret_cast<const void*>(tattn_fused_kernel<__VA_ARGS__, true>) : reinterpret_cast<const void*>(tattn_fused_kernel<__VA_ARGS__, false>))
+  if (C == 320 && p.hp == 96 && !q8) { fn = UDT_TATTN_FN(64, 5, 6, false); which = 0; }
+  else if (C == 640 && p.hp == 160) { fn = q8 ? UDT_TATTN_FN(32, 10, 10, true) : UDT_TATTN_FN(32, 10, 10, false); which = q8 ? 3 : 1; }
+  else if (C == 1280 && p.hp == 320) { fn = q8 ? UDT_TATTN_FN(32, 20, 20, true) : UDT_TATTN_FN(32, 20, 20, false); which = q8 ? 4 : 2; }
+#undef UDT_TATTN_FN
   else return UDT_ERR_BAD_SHAPE;
+  if (with_maps) which += 5;
   if (!attr_done[which]) {
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     if (e != hipSuccess) return udt_set_hip_error(e);
@@ -495,4 +527,16 @@ extern "C" int udt_tattn_fused_q8(const void* x, void* out, const void* A, const
                                   void* q8_scale, float* rowstat_out, void* stream) {
   if (!q8_out) return UDT_ERR_BAD_ARG;
   return tattn_launch(x, out, A, sc, BmT, bias, B, n_tok, C, heads, zero_samples, eps, q8_out, q8_scale, rowstat_out, stream);
+}
+
+// udt_tattn_fused (q8_out == NULL) or udt_tattn_fused_q8 (q8_out != NULL) that ALSO writes the head-mean attention maps.
+// ROUNDING: out / q8_out / rowstat_out are the bits of the plain entry points.  maps: the probabilities are the bf16 P tile the output
+// GEMM reads (each P rounded to bf16 once, round-to-nearest-even); heads summed in ascending order in fp32; the sum times
+// fp32(weight / heads), rounded; accumulate adds that to the fp32 value in place, rounded once more.
+extern "C" int udt_tattn_fused_maps(const void* x, void* out, const void* A, const float* sc, const void* BmT, const float* bias,
+                                    int32_t B, int32_t n_tok, int32_t C, int32_t heads, int32_t zero_samples, float eps, float* maps,
+                                    int32_t L, int32_t map_from, float weight, int32_t accumulate, void* q8_out, void* q8_scale,
+                                    float* rowstat_out, void* stream) {
+  return tattn_launch(x, out, A, sc, BmT, bias, B, n_tok, C, heads, zero_samples, eps, q8_out, q8_scale, rowstat_out, stream, true, maps, L,
+                      map_from, weight, accumulate);
 }

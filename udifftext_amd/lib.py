@@ -114,6 +114,8 @@ SYMBOLS = {
     "udt_tattn_fused": (C.c_int, [_vp, _vp, _vp, _fp, _vp, _fp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "udt_tattn_rowstat_parts": (_i32, [_i32, _i32, _i32]),
     "udt_tattn_fused_q8": (C.c_int, [_vp, _vp, _vp, _fp, _vp, _fp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _fp, _vp]),
+    "udt_tattn_fused_maps": (C.c_int, [_vp, _vp, _vp, _fp, _vp, _fp, _i32, _i32, _i32, _i32, _i32, _f32, _fp, _i32, _i32, _f32, _i32,
+                                       _vp, _vp, _fp, _vp]),
     "udt_gn_nchunks": (_i32, [_i64, _i32]),
     "udt_gn_stats": (C.c_int, [_vp, _vp, _fp, _i32, _i64, _i32, _i32, _i32, _vp]),
     "udt_gn_apply": (C.c_int, [_vp, _vp, _vp, _fp, _fp, _fp, _i32, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
@@ -158,6 +160,7 @@ SYMBOLS = {
     "udt_aae_row_update_f32": (C.c_int, [_fp, _fp, _fp, _vp, _vp, _vp, _i32, _i64, _f32, _f32, _i32, _i32, _vp]),
     "udt_crop_resize_aa_f32": (C.c_int, [_fp, _vp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),
     "udt_crop_resize_aa_bwd_f32": (C.c_int, [_fp, _vp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "udt_resize_bilinear_f32": (C.c_int, [_fp, _fp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "udt_mattn_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _vp, _i32, _i32, _i32, _i32, _i32,
                                 _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp]),
     "udt_gelu_fwd": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),

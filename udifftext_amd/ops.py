@@ -659,6 +659,36 @@ def tattn_fused(x: torch.Tensor, tables: Optional[TattnTables], bias: torch.Tens
     return out
 
 
+def tattn_fused_maps(x: torch.Tensor, tables: TattnTables, bias: torch.Tensor, heads: int, zero_samples: int, eps: float,
+                     maps: torch.Tensor, map_from: int, weight: float = 1.0, accumulate: bool = False,
+                     out: Optional[torch.Tensor] = None, emit_q8: bool = False) -> torch.Tensor:
+    """``tattn_fused`` (same operands, bit-identical result and sidecars) that also writes the head-mean attention maps of the samples
+    >= map_from into the caller's ``maps`` fp32 [B - map_from, L, N] (udt_tattn_fused_maps): ``weight / heads * sum_h P``, stored, or
+    added to what ``maps`` holds with ``accumulate``.  L = maps.shape[1] is the context length the tables were prepared for."""
+    _bf16(x)
+    assert x.is_contiguous()
+    B, N, Cc = x.shape
+    out = _drop_sidecars(out) if out is not None else torch.empty_like(x)
+    assert out.is_contiguous()
+    assert tables is not None and tables.A.is_contiguous() and tables.sc.is_contiguous() and tables.BmT.is_contiguous()
+    assert tables.A.shape[0] == B
+    assert maps.dtype == torch.float32 and maps.dim() == 3 and maps.is_contiguous() and maps.device == x.device
+    assert maps.shape[0] == B - map_from and maps.shape[2] == N, f"maps {tuple(maps.shape)} for B={B} map_from={map_from} N={N}"
+    Lc = maps.shape[1]
+    q = None
+    parts = L.load().udt_tattn_rowstat_parts(B, N, Cc) if emit_q8 else 0
+    if parts > 0:
+        q = _mx8_alloc(B * N, Cc, x.device)
+        q = Mx8Act(q.data, q.scale, torch.empty((parts, B * N, 2), dtype=torch.float32, device=x.device))
+    L.check(L.load().udt_tattn_fused_maps(_ptr(x), _ptr(out), _ptr(tables.A), _ptr(tables.sc), _ptr(tables.BmT), _ptr(bias), B, N, Cc, heads,
+                                          zero_samples, eps, _ptr(maps), Lc, map_from, float(weight), int(bool(accumulate)),
+                                          _ptr(q.data) if q else None, _ptr(q.scale) if q else None, _ptr(q.stats) if q else None,
+                                          _stream()), "udt_tattn_fused_maps")
+    if q is not None:
+        out.mx8 = q
+    return out
+
+
 def softmax_rows_(x: torch.Tensor) -> torch.Tensor:
     _bf16(x)
     assert x.is_contiguous()
@@ -974,6 +1004,21 @@ def crop_resize_aa(img: torch.Tensor, boxes: torch.Tensor, out_hw, mul: float = 
     out = torch.empty((N, Cc, oh, ow), dtype=torch.float32, device=img.device)
     L.check(L.load().udt_crop_resize_aa_f32(_ptr(img), _ptr(boxes), _ptr(out), B, Cc, H, W_, N, oh, ow, float(mul), float(add), _stream()),
             "udt_crop_resize_aa_f32")
+    return out
+
+
+def resize_bilinear(x: torch.Tensor, out_hw, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bilinear resize (half-pixel centres, edge clamp, no antialiasing) of every [h, w] plane of x fp32 [..., h, w] to ``out_hw`` in one
+    launch (udt_resize_bilinear_f32) -> fp32 [..., H, W]"""
+    assert x.dtype == torch.float32 and x.dim() >= 2 and x.is_contiguous()
+    h, w = x.shape[-2:]
+    H, W_ = (int(v) for v in out_hw)
+    shape = tuple(x.shape[:-2]) + (H, W_)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous() and out.device == x.device
+    planes = x.numel() // (h * w) if h * w else 0
+    L.check(L.load().udt_resize_bilinear_f32(_ptr(x), _ptr(out), planes, h, w, H, W_, _stream()), "udt_resize_bilinear_f32")
     return out
 
 

@@ -76,6 +76,8 @@ def predict_sharded(cfgs, model, sampler, global_batches: Sequence[dict], global
     ``micro_batch`` images (config #3: 8 images per GPU = two batches of 4, sampled concurrently on two launch
     streams) and hands them to ``predict_many`` (default: pipeline.predict_many) with per-image seeds; then ONE
     all-gather per global batch collects the decoded frames.  ``cfgs.batch_size`` is set per micro-batch."""
+    if getattr(cfgs, "detailed", False):
+        raise NotImplementedError("detailed character maps are not gathered across ranks: call pipeline.predict_many per rank")
     if predict_many is None:
         from udifftext_amd import pipeline
         predict_many = pipeline.predict_many

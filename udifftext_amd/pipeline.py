@@ -191,29 +191,78 @@ def _form_batch(cfgs, model, sampler, batches, image_seeds, idx, device, masks=F
     return cat(xs), cat_cond(cs), cat_cond(ucs), fb, kw, [x.shape[0] for x in xs], (xs, cs, ucs, noises)
 
 
-def _split(img, z, sizes):
-    """the fused batch's outputs back per input batch"""
+def _split(img, z, sizes, maps=None):
+    """the fused batch's outputs back per input batch (triples with the character maps of a ``cfgs.detailed`` run)"""
     bounds = [sum(sizes[:k]) for k in range(len(sizes) + 1)]
+    if maps is not None:
+        return [(img[a:b], z[a:b], maps[a:b]) for a, b in zip(bounds, bounds[1:])]
     return [(img[a:b], z[a:b]) for a, b in zip(bounds, bounds[1:])]
 
 
-def _predict_many_aae(cfgs, model, sampler, sample_rows, batches, units, device, image_seeds, record_losses):
+def _map_size(map_size, img):
+    """``predict_many``'s map_size -> None | (H, W)"""
+    if map_size is None:
+        return None
+    if isinstance(map_size, str):
+        if map_size != "image":
+            raise ValueError(f"map_size must be None, 'image' or (H, W), not {map_size!r}")
+        return tuple(int(v) for v in img.shape[-2:])
+    H, W = (int(v) for v in map_size)
+    if H < 1 or W < 1:
+        raise ValueError(f"map_size {map_size!r}: both sides must be at least 1")
+    return H, W
+
+
+def _resize_maps(maps, map_size, img):
+    """character maps [B, L, h, w] at ``map_size`` (udt_resize_bilinear_f32: one launch for all planes, on the current stream)"""
+    hw = _map_size(map_size, img)
+    if hw is None or maps is None:
+        return maps
+    from udifftext_amd import ops
+    return ops.resize_bilinear(maps.contiguous(), hw)
+
+
+def save_char_maps(maps, labels, names, out_dir="./temp/seg_map"):
+    """the file ``EulerEDMSampler.save_segment_map`` writes (reference sampling.py:254-262), one per image: maps [B, L, h, w] (one
+    batch of ``predict_many``'s third output), labels / names one string per image -> ``out_dir``/seg_<name>.npy holding the first
+    len(label) planes, fp32 [len(label), h, w].  Host side only; returns the paths."""
+    import os
+
+    import numpy as np
+    arr = maps.detach().float().cpu().numpy() if isinstance(maps, torch.Tensor) else np.asarray(maps, dtype=np.float32)
+    if not (arr.ndim == 4 and arr.shape[0] == len(labels) == len(names)):
+        raise ValueError(f"maps {arr.shape} for {len(labels)} labels and {len(names)} names")
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for m, label, name in zip(arr, labels, names):
+        if len(label) > m.shape[0]:
+            raise ValueError(f"label {label!r} has {len(label)} characters, the maps hold {m.shape[0]}")
+        paths.append(os.path.join(out_dir, f"seg_{name}.npy"))
+        np.save(paths[-1], np.stack([m[i] for i in range(len(label))]) if len(label) else m[:0])
+    return paths
+
+
+def _predict_many_aae(cfgs, model, sampler, sample_rows, batches, units, device, image_seeds, record_losses, map_size=None):
     """the attend-and-excite branch of ``predict_many``: sampling batch after sampling batch on the current stream (see there)"""
     from udifftext_amd import ops
     out = []
     for idx in units:
         with ops.launch_context(cu_share=1):
             fx, fc, fuc, fb, kw, sizes, _ = _form_batch(cfgs, model, sampler, batches, image_seeds, idx, device, masks=True)
+            if cfgs.detailed:
+                kw["char_maps"] = True
             z = sample_rows(model, fx, fc, fb, fuc, init_step=cfgs.init_step, record_losses=record_losses, **kw)
+            z, maps = z if cfgs.detailed else (z, None)
             img = torch.clamp((model.decode_first_stage(z) + 1.0) / 2.0, min=0.0, max=1.0)
-        out.extend(_split(img, z, sizes))
+            maps = _resize_maps(maps, map_size, img)
+        out.extend(_split(img, z, sizes, maps))
     if torch.device(device).type == "cuda":
         ops.check_async_errors()
     return out
 
 
 def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] = None, in_flight: Optional[int] = None,
-                 fuse: Optional[int] = None, image_seeds: Optional[list] = None, record_losses: bool = True):
+                 fuse: Optional[int] = None, image_seeds: Optional[list] = None, record_losses: bool = True, map_size=None):
     """``predict`` over a list of batches in throughput mode: ``fuse`` consecutive batches are concatenated into one
     sampling batch, and up to ``in_flight`` such batches are processed concurrently, each on its own launch stream
     (a lane): conditioning (VAE encoder, label encoder), the sampling loop's hipGraph replays (EulerEDMSampler.sample_lane)
@@ -229,7 +278,15 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
     loop reads one word back per iterated update, and a host blocked on that read cannot feed other lanes.  Every image runs its own
     update loop inside the fused batch (EulerEDMSampler.attend_and_excite_rows), so its result still depends on its own inputs
     alone.  ``record_losses`` goes to the sampler (per-row local losses of every step in ``sampler.last_row_losses``, of the last
-    sampling batch).  ``cfgs.detailed`` is refused."""
+    sampling batch).
+    ``cfgs.detailed`` (the reference's per-character attention maps, sampling.py:344-346,380): every output becomes
+    (samples, z, maps) with maps fp32 [B_k, L, h_map, w_map] — for EVERY image, the head mean of the configured t_attn layers'
+    probabilities at the middle step, written by that step's fused text attention inside the replayed graph
+    (udt_tattn_fused_maps); samples and z have the bits of the run without ``detailed``.  ``map_size``: None (the layer's own
+    grid), "image" or (H, W) — the maps resized bilinearly on the lane before the final synchronisation
+    (udt_resize_bilinear_f32).  ``save_char_maps`` writes the reference's seg_<name>.npy files from them.  ValueError, before
+    anything is sampled, when cfgs.init_step lies behind the middle step; NotImplementedError for a sampler that hands back no
+    maps.  With ``cfgs.aae_enabled`` too, the maps are the same reduction of the probabilities the middle step cached."""
     from udifftext_amd import ops
     device = device or next(model.parameters()).device
     n = max(1, int(in_flight if in_flight is not None else IN_FLIGHT))
@@ -237,8 +294,15 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
     auto = f <= 0
     if auto:
         f = min(4, max(1, -(-len(batches) // n)))
-    if cfgs.detailed:
-        raise NotImplementedError("detailed dumps are out of scope (see EulerEDMSampler.__call__)")
+    detailed = bool(cfgs.detailed)
+    if detailed:
+        if not hasattr(sampler, "char_map_step"):
+            raise NotImplementedError(f"cfgs.detailed in predict_many needs a sampler that hands back character maps "
+                                      f"(char_map_step, sample_lane(char_maps=True)), not {type(sampler).__name__}")
+        sampler.char_map_step(cfgs.init_step)              # ValueError: the run would start behind the step that emits the maps
+    elif map_size is not None:
+        raise ValueError("map_size resizes the character maps of a cfgs.detailed run; cfgs.detailed is not set")
+    _map_size(map_size, torch.empty((1, 1)))               # (a malformed map_size raises before anything is sampled)
     aae_sampler = getattr(sampler, "sample_rows_with_attend_and_excite", None) if cfgs.aae_enabled else None
     if cfgs.aae_enabled and aae_sampler is None:
         raise NotImplementedError(f"attend-and-excite in predict_many needs a sampler with sample_rows_with_attend_and_excite "
@@ -270,7 +334,7 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
     else:
         units = [list(range(i, min(i + f, len(batches)))) for i in range(0, len(batches), f)]
     if aae_sampler is not None:
-        return _predict_many_aae(cfgs, model, sampler, aae_sampler, batches, units, device, image_seeds, record_losses)
+        return _predict_many_aae(cfgs, model, sampler, aae_sampler, batches, units, device, image_seeds, record_losses, map_size)
     # lanes in use: as few as keep every lane equally loaded — 4 sampling batches on 3 lanes run as 2 + 2 on TWO lanes (each planned
     # for half of the CUs), not as 2 + 1 + 1 with the 4th batch alone on a lane planned for a third of the chip while two lanes idle
     rounds = -(-len(units) // n) if units else 1
@@ -281,14 +345,19 @@ def predict_many(cfgs, model, sampler, batches, device: Optional[torch.device] =
         lane = lanes[u % n_used]
         with on(lane), ops.launch_context(cu_share=n_used):
             fx, fc, fuc, _, kw, sizes, parts = _form_batch(cfgs, model, sampler, batches, image_seeds, idx, device)
+            if detailed:
+                kw["char_maps"] = True
             if lane_sampler is not None:
                 z = lane_sampler(model, fx, fc, fuc, slot=u % n_used, n_lanes=n_used, init_step=cfgs.init_step, deferred_checks=checks,
                                  **kw)
             else:       # (stub samplers of the CPU tests: the group interface, one batch at a time)
-                z = sampler.sample_in_flight(model, [fx], [fc], [fuc], init_step=cfgs.init_step, deferred_checks=checks)[0]
+                cm = {"char_maps": True} if detailed else {}
+                z = sampler.sample_in_flight(model, [fx], [fc], [fuc], init_step=cfgs.init_step, deferred_checks=checks, **cm)[0]
+            z, maps = z if detailed else (z, None)
             img = torch.clamp((model.decode_first_stage(z) + 1.0) / 2.0, min=0.0, max=1.0)
-        keep.append((parts, fx, fc, fuc, z))                   # tensors of a lane stream: alive until the final synchronisation
-        out.extend(_split(img, z, sizes))
+            maps = _resize_maps(maps, map_size, img)
+        keep.append((parts, fx, fc, fuc, z, maps))             # tensors of a lane stream: alive until the final synchronisation
+        out.extend(_split(img, z, sizes, maps))
     for lane in lanes:
         after(main, lane)
     for chk in checks:
@@ -346,7 +415,8 @@ def evaluate(cfgs, model, sampler, batches, predictor, device: Optional[torch.de
         labels.append(lb)
         boxes.append(torch.cat((torch.arange(rb.shape[0]).reshape(-1, 1), rb), 1))       # + the image's index in its batch
     outputs = predict_many(cfgs, model, sampler, batches, device, in_flight=in_flight, fuse=fuse, image_seeds=image_seeds)
-    crops = [predictor.transform_boxes(samples, bx) for (samples, _), bx in zip(outputs, boxes)]
+    # (outputs are (samples, z), or (samples, z, maps) under cfgs.detailed: only the samples are read here)
+    crops = [predictor.transform_boxes(o[0], bx) for o, bx in zip(outputs, boxes)]
     if ocr_batch is None:
         chunks = crops
     else:

@@ -259,6 +259,9 @@ class BasicTransformerBlock(nn.Module):
         self.norm3 = H.LayerNorm(dim)
         self.ff = FeedForward(dim, dropout=dropout, glu=gated_ff)
 
+    char_map = None          # (maps fp32 [B - map_from, L, N], map_from, weight, accumulate) for the ONE UNet call that asked for this
+    #                          block's head-mean text-attention map (UnifiedUNetModel.forward_nhwc sets and clears it)
+
     def fused_tattn_ok(self, n_tokens: int) -> bool:
         C = self.t_attn.heads * self.t_attn.dim_head
         return (TATTN_FUSED and self.t_attn.dim_head == 64 and C in (320, 640, 1280) and self.t_attn.heads * 64 == C
@@ -277,7 +280,16 @@ class BasicTransformerBlock(nn.Module):
         x = self.attn1(x, residual=x, ln=self.norm1, x8=x8 if mx else None) if fold else self.attn1(self.norm1(x), residual=x)
         if hasattr(self, "t_attn"):
             n0 = 0 if emit_map else min(int(zero_ctx_rows), x.shape[0])
-            if t_fused is not None and not emit_map and n0 < x.shape[0] and self.fused_tattn_ok(x.shape[1]):
+            if self.char_map is not None:
+                # the fused launch that also writes the head mean of its probabilities (udt_tattn_fused_maps): same x, same tables,
+                # the same bits in the result as the plain fused launch below
+                if emit_map or t_fused is None or n0 >= x.shape[0] or not self.fused_tattn_ok(x.shape[1]):
+                    raise NotImplementedError(f"character maps of a t_attn layer with {x.shape[1]} tokens: the fused text attention "
+                                              "does not run here (no tables, a map-emitting call, or a token count it does not take)")
+                maps, map_from, weight, acc = self.char_map
+                _, bo = self.t_attn.to_out[0].packed()
+                x = ops.tattn_fused_maps(x, t_fused, bo, self.t_attn.heads, n0, self.t_norm.eps, maps, map_from, weight, acc, emit_q8=mx)
+            elif t_fused is not None and not emit_map and n0 < x.shape[0] and self.fused_tattn_ok(x.shape[1]):
                 _, bo = self.t_attn.to_out[0].packed()
                 x = ops.tattn_fused(x, t_fused, bo, self.t_attn.heads, n0, self.t_norm.eps, emit_q8=mx)
             elif n0 > 0 and t_kv is not None:

@@ -154,8 +154,10 @@ class UnifiedUNetModel(nn.Module):
 
         def transformer(ch, d):
             nh, dh = heads_of(ch)
-            return SpatialTransformer(ch, nh, dh, depth=d, t_context_dim=t_context_dim, v_context_dim=v_context_dim,
-                                      use_linear=use_linear_in_transformer)
+            st = SpatialTransformer(ch, nh, dh, depth=d, t_context_dim=t_context_dim, v_context_dim=v_context_dim,
+                                    use_linear=use_linear_in_transformer)
+            st.ds = ds                               # its tokens are the (h / ds) x (w / ds) grid of the latent
+            return st
 
         self.input_blocks = nn.ModuleList([TimestepEmbedSequential(H.Conv2d(in_channels, model_channels, 3, padding=1))])
         self.input_blocks[0][0].emit_colstats = True
@@ -258,6 +260,54 @@ class UnifiedUNetModel(nn.Module):
             pass
         return attn_map_i
 
+    # ------------------------------------------------------------------------------------------ character maps
+    def char_map_blocks(self, layers=None, attn_type="t_attn"):
+        """the transformer blocks whose text attention the character maps average, in launch order: [(layer name, block, ds)].
+        layers None: what ``save_attn_map`` selects (``save_attn_layers`` x ``save_attn_type``; configs: output_blocks.6.1)"""
+        if layers is None:
+            layers = self.attn_layers if attn_type in self.attn_type else []
+        out = []
+        for st_name, st in self.named_modules():
+            if isinstance(st, SpatialTransformer):
+                for i, blk in enumerate(st.transformer_blocks):
+                    name = f"{st_name}.transformer_blocks.{i}.{attn_type}"
+                    if hasattr(blk, attn_type) and any(name.startswith(b) for b in layers):
+                        out.append((name, blk, st.ds))
+        if not out:
+            raise RuntimeError("character maps: save_attn_layers / save_attn_type select no attention layer")
+        return out
+
+    def char_map_plan(self, h: int, w: int, n_ctx: int, layers=None):
+        """-> (blocks, (h_map, w_map)) for latents of h x w and a context of n_ctx tokens.  RuntimeError: nothing selected, or the
+        selected layers have different map sizes (as ``save_attn_map``); NotImplementedError: a selected layer the fused text
+        attention does not cover (its token tile, TATTN_FUSED off, or a single-token context: the sigmoid branch has no tables)"""
+        blocks = self.char_map_blocks(layers)
+        hws = {(-(-h // ds), -(-w // ds)) for _, _, ds in blocks}
+        if len(hws) != 1:
+            raise RuntimeError(f"character maps: the selected layers have different map sizes {sorted(hws)}")
+        hm, wm = next(iter(hws))
+        for name, blk, _ in blocks:
+            if not 2 <= n_ctx <= 12 or not blk.fused_tattn_ok(hm * wm):
+                raise NotImplementedError(f"character maps: {name} with {hm * wm} tokens ({hm} x {wm}) and a context of {n_ctx} "
+                                          "tokens is not covered by the fused text attention (udt_tattn_fused_maps)")
+        return blocks, (hm, wm)
+
+    def char_maps_from_cache(self, rows_from: int = 0, layers=None, attn_type="t_attn") -> torch.Tensor:
+        """``save_attn_map``'s reduction of the maps the last map-emitting call cached, for every sample >= rows_from and on the
+        device: stack the selected layers -> mean -> mean over heads -> fp32 [b, L, h_map, w_map] (torch ops: not a hot path)"""
+        blocks = self.char_map_blocks(layers, attn_type)
+        items = [getattr(blk, attn_type).attn_map_cache for _, blk, _ in blocks]
+        if any(it is None or it["attn_map"] is None for it in items):
+            raise RuntimeError("character maps: a selected layer has no cached map — run a map-emitting UNet call first")
+        hws = {it["hw"] for it in items}
+        if len(hws) != 1:
+            raise RuntimeError(f"character maps: the selected layers have different map sizes {sorted(hws)}")
+        hm, wm = next(iter(hws))
+        m = torch.stack([it["attn_map"].detach().float() for it in items], dim=0).mean(dim=0)      # [b * heads, n, l]
+        _, n, l = m.shape
+        m = m.reshape(-1, items[0]["heads"], n, l).mean(dim=1)                                     # [b, n, l]
+        return m[rows_from:].permute(0, 2, 1).reshape(-1, l, hm, wm).contiguous()
+
     def _sources(self):
         return [p for rb in self._resblocks for p in (rb.emb_layers[1].weight, rb.emb_layers[1].bias)]
 
@@ -290,18 +340,40 @@ class UnifiedUNetModel(nn.Module):
                 for i, (st, kv) in enumerate(zip(self._transformers, t_kv))]
 
     def forward_nhwc(self, xin: torch.Tensor, emb_rows: torch.Tensor, t_kv: List[list], emit_maps: bool = False,
-                     zero_ctx_rows: int = 0, t_fused: Optional[List[list]] = None) -> torch.Tensor:
+                     zero_ctx_rows: int = 0, t_fused: Optional[List[list]] = None, char_maps: Optional[torch.Tensor] = None,
+                     map_from: int = 0, map_layers=None) -> torch.Tensor:
         """xin: bf16 [B, h, w, 64] (9 real channels); returns eps fp32 [B, h, w, 4].
-        zero_ctx_rows: leading samples whose text context is exactly zero (see BasicTransformerBlock.forward)."""
+        zero_ctx_rows: leading samples whose text context is exactly zero (see BasicTransformerBlock.forward).
+        char_maps: caller-owned fp32 [B - map_from, L, h_map * w_map] (or [.., h_map, w_map]) that this call fills with the head and
+        layer mean of the text-attention probabilities of ``map_layers`` (default: ``char_map_blocks``) for the samples >= map_from
+        (>= zero_ctx_rows), L the context length; those layers take udt_tattn_fused_maps, every other launch is what it is without."""
+        asked = []
+        if char_maps is not None:
+            B, hl, wl, _ = xin.shape
+            if emit_maps or t_fused is None:
+                raise NotImplementedError("character maps come out of the fused text attention: not from a map-emitting call, and not "
+                                          "without its tables")
+            blocks, (hm, wm) = self.char_map_plan(hl, wl, char_maps.shape[1], map_layers)
+            assert char_maps.dtype == torch.float32 and char_maps.is_contiguous()
+            assert char_maps.shape[0] == B - map_from and char_maps[0, 0].numel() == hm * wm and map_from >= min(zero_ctx_rows, B), \
+                f"char_maps {tuple(char_maps.shape)}: expected [{B - map_from}, L, {hm} * {wm}] with map_from >= {zero_ctx_rows}"
+            flat = char_maps.view(char_maps.shape[0], char_maps.shape[1], hm * wm)
+            for i, (_, blk, _) in enumerate(blocks):
+                blk.char_map = (flat, int(map_from), 1.0 / len(blocks), i > 0)
+                asked.append(blk)
         hs = []
         h = xin
         kw = dict(t_kv=t_kv, emit_map=emit_maps, zero_ctx_rows=zero_ctx_rows, t_fused=t_fused)
-        for block in self.input_blocks:
-            h = block(h, emb_rows, **kw)
-            hs.append(h)
-        h = self.middle_block(h, emb_rows, **kw)
-        for block in self.output_blocks:
-            h = block(h, emb_rows, x2=hs.pop(), **kw)
+        try:
+            for block in self.input_blocks:
+                h = block(h, emb_rows, **kw)
+                hs.append(h)
+            h = self.middle_block(h, emb_rows, **kw)
+            for block in self.output_blocks:
+                h = block(h, emb_rows, x2=hs.pop(), **kw)
+        finally:
+            for blk in asked:
+                blk.char_map = None
         return self.out[2](h, norm=self.out[0], norm_silu=True, flags=H.GEMM_OUT_F32, colstats=False)
 
     def forward(self, x, timesteps=None, t_context=None, v_context=None, y=None, **kwargs):

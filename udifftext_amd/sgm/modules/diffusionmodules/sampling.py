@@ -214,6 +214,7 @@ class EulerEval(NamedTuple):
     sigma_next: float
     src: str = "x"
     churn: float = 0.0                 # != 0: src += churn * noise[slot] before the evaluation (udt_unet_input_churn)
+    maps: bool = False                 # this evaluation's UNet call also emits the character maps (udt_tattn_fused_maps)
 
 
 class Eval(NamedTuple):
@@ -231,6 +232,7 @@ class Eval(NamedTuple):
     kn: float = 0.0
     den_out: Optional[str] = None
     churn: float = 0.0                 # as EulerEval.churn (set by no sampler yet: Heun churn would be a plan change only)
+    maps: bool = False                 # as EulerEval.maps
 
 
 class MultistepEval(NamedTuple):
@@ -242,6 +244,7 @@ class MultistepEval(NamedTuple):
     d_out: str
     k0: float
     hist: tuple = ()
+    maps: bool = False                 # as EulerEval.maps
 
 
 def plan_buffers(plans) -> list:
@@ -273,6 +276,28 @@ def plan_noise_slots(plans) -> Dict[int, int]:
     return {i: k for k, i in enumerate(churned)}
 
 
+def char_map_step(n_sigmas: int, init_step: int = 0) -> int:
+    """the step whose first evaluation emits the character maps: the middle one, (n_sigmas - 1) // 2 (reference sampling.py:380);
+    ValueError when the run starts behind it"""
+    mid = (n_sigmas - 1) // 2
+    if init_step > mid:
+        raise ValueError(f"character maps are taken at step {mid} of {n_sigmas - 1}; init_step {init_step} starts behind it")
+    return mid
+
+
+def plans_with_char_maps(plans, n_sigmas: int, init_step: int = 0) -> list:
+    """``plans`` with the first evaluation of the middle step carrying ``maps`` (captured runners are keyed by their plans: such a
+    run has a runner of its own, and that step's graph holds the map-emitting launches)"""
+    mid = char_map_step(n_sigmas, init_step)
+    out = [(i, ((plan[0]._replace(maps=True),) + tuple(plan[1:])) if i == mid else plan) for i, plan in plans]
+    assert sum(e.maps for _, plan in out for e in plan) == 1, f"step {mid} is not among the plans"
+    return out
+
+
+def plans_emit_maps(plans) -> bool:
+    return any(e.maps for _, plan in plans for e in plan)
+
+
 def plans_add_noise(plans) -> bool:
     """does an evaluation of ``plans`` read a draw (ancestral noise after the update, or churn before the evaluation)?"""
     return bool(plan_noise_slots(plans))
@@ -298,6 +323,8 @@ class _Stepper:
         # EpsScaling + DiscreteDenoiser + VanillaCFG: the udt_cfg_* launches; anything else: udt_precond_* (same count per evaluation)
         self.eps_cfg = self.pair and type(self.den) is DiscreteDenoiser and type(self.den.scaling) is EpsScaling
         ctx = torch.cat((uc["t_crossattn"], cond["t_crossattn"]), 0) if self.pair else cond["t_crossattn"]
+        self.ctx_len = int(ctx.shape[1])
+        self.latent_hw = (int(h), int(w))
         self.t_kv = self.unet.project_context(ctx)                        # hoisted k|v of all transformers
         self.t_fused = self.unet.prepare_fused_tattn(self.t_kv)           # ... folded further into the fused t_attn tables
         # force_uc_zero_embeddings=["label"] (reference sample loop) makes the unconditional context exactly zero:
@@ -342,11 +369,18 @@ class _Stepper:
             self._emb_cache[c_noise] = rows
         return rows
 
+    def new_char_maps(self) -> torch.Tensor:
+        """a buffer for the character maps of one evaluation: fp32 [B, L, h_map, w_map], one entry per image (the conditional rows).
+        Raises what ``UnifiedUNetModel.char_map_plan`` raises — before anything is launched or captured"""
+        _, (hm, wm) = self.unet.char_map_plan(*self.latent_hw, self.ctx_len)
+        return torch.zeros((self.B, self.ctx_len, hm, wm), dtype=torch.float32, device=self.dev)
+
     def unet_eps(self, x: torch.Tensor, sigma: float, emit_maps: bool = False, churn: float = 0.0,
-                 noise: Optional[torch.Tensor] = None):
+                 noise: Optional[torch.Tensor] = None, char_maps: Optional[torch.Tensor] = None):
         """the UNet call on x (fp32 NCHW [B,4,h,w]) at the denoiser's (possibly quantised) sigma -> (network output fp32 NHWC
         [rows,h,w,ld] — the CFG pair's 2B rows or, unguided, B —, the evaluation's ``Precond``); churn != 0: x += churn * noise
-        first, in the same launch that packs the UNet input"""
+        first, in the same launch that packs the UNet input.  char_maps (``new_char_maps``): the call also writes the head-mean
+        text-attention maps of the conditional rows there — the selected layers take udt_tattn_fused_maps, eps has the same bits"""
         k = self.coefs(sigma)
         if churn != 0.0 and noise is None:
             raise ValueError("a churned evaluation needs the step's draw (draw_step_noise)")
@@ -360,34 +394,40 @@ class _Stepper:
             self.unet.clear_attn_map()
         emb = self.emb_rows(k.c_noise)
         if self.dual and not emit_maps:
-            eps = self._forward_two_streams(emb)
+            eps = self._forward_two_streams(emb, char_maps)
         else:
             with ops.launch_context(cu_share=self.cu_share, workspace=self.ws):
-                eps = self.unet.forward_nhwc(self.xin, emb, self.t_kv, emit_maps=emit_maps,
-                                             zero_ctx_rows=self.zero_ctx_rows, t_fused=self.t_fused)
+                # one stream: the conditional rows are the pair's second half, whether or not the unconditional context is zero
+                eps = self.unet.forward_nhwc(self.xin, emb, self.t_kv, emit_maps=emit_maps, zero_ctx_rows=self.zero_ctx_rows,
+                                             t_fused=self.t_fused, char_maps=char_maps, map_from=self.B if self.pair else 0)
         return eps, k
 
     def step(self, x: torch.Tensor, sigma: float, sigma_next: float, emit_maps: bool = False,
-             denoised: Optional[torch.Tensor] = None, churn: float = 0.0, noise: Optional[torch.Tensor] = None) -> None:
+             denoised: Optional[torch.Tensor] = None, churn: float = 0.0, noise: Optional[torch.Tensor] = None,
+             char_maps: Optional[torch.Tensor] = None) -> None:
         """in-place Euler update of x (fp32 NCHW [B,4,h,w]) from sigma (sigma_hat on a churned step: x += churn * noise before
         the evaluation) to sigma_next; denoised (optional): receives the guided denoised latent"""
-        eps, k = self.unet_eps(x, sigma, emit_maps, churn, noise)
+        eps, k = self.unet_eps(x, sigma, emit_maps, churn, noise, char_maps)
         if self.eps_cfg:
             ops.cfg_euler_step(x, eps, sigma, sigma_next, self.scale, denoised=denoised, c_out=k.c_out)
         else:
             ops.precond_euler_step(x, eps, k.c_skip, k.c_out, sigma, sigma_next, self.scale, self.pair, denoised=denoised)
 
-    def run_plan(self, bufs: Dict[str, torch.Tensor], plan, noise: Optional[torch.Tensor] = None) -> None:
+    def run_plan(self, bufs: Dict[str, torch.Tensor], plan, noise: Optional[torch.Tensor] = None,
+                 char_maps: Optional[torch.Tensor] = None) -> None:
         """one sampler step: per evaluation of ``plan`` (a tuple of ``EulerEval`` / ``Eval`` / ``MultistepEval``), the UNet call
         on its source buffer and its fused launch; ``bufs`` maps the plan's buffer names to fp32 NCHW tensors, ``noise`` is this
-        step's draw (ancestral or churn: plan_noise_slots)"""
+        step's draw (ancestral or churn: plan_noise_slots), ``char_maps`` (``new_char_maps``) what an evaluation with ``maps`` fills"""
         for e in plan:
             src = bufs[e.src]
+            cm = char_maps if e.maps else None
+            if e.maps and cm is None:
+                raise ValueError("an evaluation of the plan emits character maps and no buffer was given (new_char_maps)")
             if isinstance(e, EulerEval):
-                self.step(src, e.sigma, e.sigma_next, churn=e.churn, noise=noise)
+                self.step(src, e.sigma, e.sigma_next, churn=e.churn, noise=noise, char_maps=cm)
                 continue
             if isinstance(e, MultistepEval):
-                eps, k = self.unet_eps(src, e.sigma)
+                eps, k = self.unet_eps(src, e.sigma, char_maps=cm)
                 ms = dict(hist=[bufs[b] for b, _ in e.hist], d_out=bufs[e.d_out], out=bufs[e.out])
                 ks = (e.k0,) + tuple(kj for _, kj in e.hist)
                 if self.eps_cfg:
@@ -395,7 +435,7 @@ class _Stepper:
                 else:
                     ops.precond_multistep_step(src, eps, k.c_skip, k.c_out, self.scale, self.pair, e.sigma, ks, **ms)
                 continue
-            eps, k = self.unet_eps(src, e.sigma, churn=e.churn, noise=noise)
+            eps, k = self.unet_eps(src, e.sigma, churn=e.churn, noise=noise, char_maps=cm)
             terms = dict(aux=bufs[e.aux] if e.aux else None, ka=e.ka, prev=bufs[e.prev] if e.prev else None, kp=e.kp,
                          noise=noise if e.kn != 0.0 else None, kn=e.kn, out=bufs[e.out],
                          denoised=bufs[e.den_out] if e.den_out else None)
@@ -410,15 +450,17 @@ class _Stepper:
         if self.ws_side is not None:
             self.ws_side.check(self.side.cuda_stream)
 
-    def _forward_two_streams(self, emb: torch.Tensor) -> torch.Tensor:
+    def _forward_two_streams(self, emb: torch.Tensor, char_maps: Optional[torch.Tensor] = None) -> torch.Tensor:
         """uc half on the current stream, c half on the side stream (fork / join; captured as two graph branches);
-        the stream-K kernels of both streams must be co-resident: each is planned for half of this stepper's CUs"""
+        the stream-K kernels of both streams must be co-resident: each is planned for half of this stepper's CUs.
+        char_maps: written by the conditional half, from the side stream (its rows are that call's whole batch: map_from 0)"""
         B = self.B
         main = torch.cuda.current_stream()
         share = 2 * self.cu_share
         self.side.wait_stream(main)
         with torch.cuda.stream(self.side), ops.launch_context(cu_share=share, workspace=self.ws_side):
-            eps_c = self.unet.forward_nhwc(self.xin[B:], emb[B:], self.t_kv_c, zero_ctx_rows=0, t_fused=self.t_fused_c)
+            eps_c = self.unet.forward_nhwc(self.xin[B:], emb[B:], self.t_kv_c, zero_ctx_rows=0, t_fused=self.t_fused_c,
+                                           char_maps=char_maps, map_from=0)
             self.eps[B:].copy_(eps_c)
         with ops.launch_context(cu_share=share, workspace=self.ws):
             eps_u = self.unet.forward_nhwc(self.xin[:B], emb[:B], self.t_kv_u, zero_ctx_rows=self.zero_ctx_rows,
@@ -458,6 +500,8 @@ class _GraphedSteps:
         self.slots = plan_noise_slots(plans)
         self.noise = (torch.zeros((len(self.slots),) + tuple(self.x.shape), dtype=torch.float32, device=self.st.dev)
                       if self.slots else None)
+        # character maps: a static fp32 [B, L, h_map, w_map] buffer the graph of the step that carries ``maps`` writes
+        self.maps = self.st.new_char_maps() if plans_emit_maps(plans) else None
         self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self.pool = torch.cuda.graph_pool_handle()
         self.capture_stream = torch.cuda.Stream(device=self.st.dev)
@@ -495,7 +539,7 @@ class _GraphedSteps:
             torch.cuda.synchronize()
             with torch.cuda.stream(self.capture_stream):
                 keep = {k: v.clone() for k, v in self.bufs.items()}
-                st.run_plan(self.bufs, plan, noise)
+                st.run_plan(self.bufs, plan, noise, self.maps)
                 for k, v in keep.items():
                     self.bufs[k].copy_(v)
             torch.cuda.synchronize()
@@ -504,7 +548,7 @@ class _GraphedSteps:
         # thread_local: other threads of the process (the RCCL watchdog under torch.distributed) may touch the
         # HIP runtime while this thread captures
         with torch.cuda.graph(g, pool=self.pool, stream=self.capture_stream, capture_error_mode="thread_local"):
-            st.run_plan(self.bufs, plan, noise)
+            st.run_plan(self.bufs, plan, noise, self.maps)
         self.graphs[i] = g
         return g
 
@@ -546,8 +590,16 @@ class _PlanSampler:
         """the evaluations of step i (sig: host sigmas, len num_steps + 1) -> tuple of EulerEval / Eval / MultistepEval"""
         raise NotImplementedError
 
-    def plans(self, sig, init_step: int = 0):
-        return [(i, self.step_plan(sig, i, init_step)) for i in self.get_sigma_gen(len(sig), init_step=init_step)]
+    def plans(self, sig, init_step: int = 0, char_maps: bool = False):
+        """char_maps: the first evaluation of the middle step carries ``maps`` (ValueError if init_step lies behind that step)"""
+        if char_maps:
+            char_map_step(len(sig), init_step)             # (before the generator below prints a progress bar)
+        plans = [(i, self.step_plan(sig, i, init_step)) for i in self.get_sigma_gen(len(sig), init_step=init_step)]
+        return plans_with_char_maps(plans, len(sig), init_step) if char_maps else plans
+
+    def char_map_step(self, init_step: int = 0, num_steps=None) -> int:
+        """the step at which a run with character maps takes them; ValueError if init_step lies behind it (host only)"""
+        return char_map_step(len(self._host_sigmas(num_steps)), init_step)
 
     def _host_sigmas(self, num_steps=None):
         n = self.num_steps if num_steps is None else num_steps
@@ -660,11 +712,22 @@ class _PlanSampler:
         if aae_enabled:
             raise NotImplementedError(f"attend-and-excite is implemented for EulerEDMSampler only, not {type(self).__name__}")
         if detailed:
-            raise NotImplementedError(f"detailed attention-map dumps are implemented for EulerEDMSampler only, not {type(self).__name__}")
+            # the per-character maps of every image, out of the middle step's fused text attention, stay on the sampler as
+            # ``last_char_maps`` (fp32 [B, L, h_map, w_map]); the PNG / .npy dumps are EulerEDMSampler's
+            x, self.last_char_maps = self._sample(denoiser, x, cond, uc, num_steps, init_step, noise, char_maps=True)
+            return x
         return self._sample(denoiser, x, cond, uc, num_steps, init_step, noise)
 
-    def _sample(self, model, x, cond, uc=None, num_steps=None, init_step=0, noise: Optional[torch.Tensor] = None):
-        """the plain sampling loop: hipGraph replay, eager launches if graphs are off or unavailable"""
+    def _sample(self, model, x, cond, uc=None, num_steps=None, init_step=0, noise: Optional[torch.Tensor] = None,
+                char_maps: bool = False):
+        """the plain sampling loop: hipGraph replay, eager launches if graphs are off or unavailable.  char_maps: -> (x, maps), the
+        head-mean text-attention maps of every image at the middle step (fp32 [B, L, h_map, w_map]); x has the bits of the run
+        that did not ask"""
+        if char_maps and model is None:
+            raise NotImplementedError("detailed character maps come out of the engine's UNet (its save_attn_layers select the "
+                                      "layers) and no engine was given")
+        if char_maps:
+            self.char_map_step(init_step, num_steps)       # ValueError before anything is launched
         self._check_fast_path(model)
         require_gpu(x, type(self).__name__)
         uc = default(uc, cond)
@@ -673,27 +736,29 @@ class _PlanSampler:
         if noise is None:
             noise = self.draw_step_noise(x.shape, x.device, num_steps, init_step)
         x *= (1.0 + sig[0] ** 2.0) ** 0.5                                  # in place, like the reference :54
-        plans = self.plans(sig, init_step)
+        plans = self.plans(sig, init_step, char_maps)
         if self.use_graphs:
             out = self._run_graphed(model, x, cond, uc, sig, plans, noise)
             if out is not None:
                 return out
         stepper = _Stepper(model, cond, uc, x.shape[0], x.shape[2:], self._scale, pair=self._pair)
+        maps = stepper.new_char_maps() if char_maps else None
         bufs = {"x": x}
         for name in plan_buffers(plans):
             bufs[name] = torch.empty_like(x)
         slots = plan_noise_slots(plans)
         for i, plan in plans:
-            stepper.run_plan(bufs, plan, noise[slots[i]] if noise is not None and i in slots else None)
+            stepper.run_plan(bufs, plan, noise[slots[i]] if noise is not None and i in slots else None, maps)
         stepper.check()
-        return x
+        return (x, maps) if char_maps else x
 
     def _runner_key(self, model, x, plans, slot: int = 0, n_lanes: int = 1) -> _RunnerKey:
         return _RunnerKey(id(model), tuple(x.shape), self._scale, x.device.index, tuple(plans), slot, n_lanes,
                           type(self.guider).__name__, denoiser_key(model.denoiser))
 
     def _run_graphed(self, model, x, cond, uc, sig, plans, noise):
-        """replay (capturing on first use) the hipGraphs of this sampling configuration; None -> eager launches"""
+        """replay (capturing on first use) the hipGraphs of this sampling configuration; None -> eager launches.  Plans that
+        emit character maps: -> (x, maps), both cloned from the runner's static buffers"""
         key = self._runner_key(model, x, plans)
         cache = self.__dict__.setdefault("_graphed", {})
         try:
@@ -708,7 +773,7 @@ class _PlanSampler:
             gs.capture()
             for i in gs.plans:
                 gs.graphs[i].replay()
-            out = gs.x.clone()
+            out = gs.x.clone() if gs.maps is None else (gs.x.clone(), gs.maps.clone())
             gs.st.check()                       # one sync per sampling loop: surfaces a stream-K time-out as UdtError
             return out
         except RuntimeError as e:
@@ -759,32 +824,33 @@ class _PlanSampler:
             deferred_checks.append(gs.st.check)
 
     def sample_lane(self, model, x, cond, uc, slot: int, n_lanes: int, init_step=0, deferred_checks: Optional[list] = None,
-                    noise: Optional[torch.Tensor] = None):
+                    noise: Optional[torch.Tensor] = None, char_maps: bool = False):
         """the sampling loop of ONE batch on the CURRENT stream, as lane ``slot`` of ``n_lanes`` free-running lanes
         (pipeline.predict_many): rebind this lane's runner to the batch, enqueue all graph replays, return the latent — no
         host synchronisation and no event shared with the other lanes, so a lane runs condition -> sample -> decode back to
         back while the launch thread is already feeding the next lane.  Launches are planned for 1 / n_lanes of the CUs
         (cu_share), as in ``sample_in_flight``.  The runner's error-word check goes to ``deferred_checks``; ``noise``: the
-        batch's ancestral draws (drawn here when not given)."""
+        batch's ancestral draws (drawn here when not given).  char_maps: -> (z, maps) as ``_sample``; the maps are cloned on the
+        lane's stream, behind the replays, before the runner serves another batch."""
         if n_lanes <= 1 or not self.use_graphs:
-            return self._sample(model, x, cond, uc, None, init_step, noise)
+            return self._sample(model, x, cond, uc, None, init_step, noise, char_maps=char_maps)
         self._check_fast_path(model)
         require_gpu(x, type(self).__name__)
         uc = default(uc, cond)
         sig = self._host_sigmas(None)
         if noise is None:
             noise = self.draw_step_noise(x.shape, x.device, None, init_step)
-        gs = self._lane_runner(model, x, cond, uc, slot, n_lanes, sig, self.plans(sig, init_step))
+        gs = self._lane_runner(model, x, cond, uc, slot, n_lanes, sig, self.plans(sig, init_step, char_maps))
         gs.load(x.float(), noise)
         gs.x.mul_((1.0 + sig[0] ** 2.0) ** 0.5)
         for i in gs.plans:
             gs.graphs[i].replay()
-        out = gs.x.clone()
+        out = gs.x.clone() if not char_maps else (gs.x.clone(), gs.maps.clone())
         self._finish(gs, torch.cuda.current_stream(), deferred_checks)
         return out
 
     def sample_in_flight(self, model, xs, conds, ucs, init_step=0, deferred_checks: Optional[list] = None,
-                         streams: Optional[list] = None, noises: Optional[list] = None):
+                         streams: Optional[list] = None, noises: Optional[list] = None, char_maps: bool = False):
         """run the sampling loops of SEVERAL independent batches concurrently (one launch stream + one set of
         hipGraphs each, every stream planned for its share of the CUs) and return their latents.
 
@@ -799,15 +865,16 @@ class _PlanSampler:
         ``streams``: launch streams to replay on, one per batch (default: the runners' capture streams).  A caller
         that already owns one stream per batch passes them so that no further streams are active: hipStreams share a
         small number of hardware queues (GPU_MAX_HW_QUEUES, 4 by default) and two busy streams on one queue serialise.
-        ``noises[k]``: batch k's ancestral draws (drawn here, in batch order, when not given)."""
+        ``noises[k]``: batch k's ancestral draws (drawn here, in batch order, when not given).
+        char_maps: every entry of the result is (z, maps) as ``_sample`` hands them back."""
         n = len(xs)
         if noises is None:
             noises = [self.draw_step_noise(x.shape, x.device, None, init_step) for x in xs]
         if n == 1 or not self.use_graphs:
-            return [self._sample(model, x, c, u, None, init_step, nz) for x, c, u, nz in zip(xs, conds, ucs, noises)]
+            return [self._sample(model, x, c, u, None, init_step, nz, char_maps=char_maps) for x, c, u, nz in zip(xs, conds, ucs, noises)]
         self._check_fast_path(model)
         sig = self._host_sigmas(None)
-        plans = self.plans(sig, init_step)
+        plans = self.plans(sig, init_step, char_maps)
         runners = []
         for slot, (x, c, u, nz) in enumerate(zip(xs, conds, ucs, noises)):
             require_gpu(x, type(self).__name__)
@@ -825,7 +892,7 @@ class _PlanSampler:
                     gs.graphs[i].replay()
         for lane in lanes:
             main.wait_stream(lane)
-        outs = [gs.x.clone() for gs in runners]
+        outs = [gs.x.clone() if not char_maps else (gs.x.clone(), gs.maps.clone()) for gs in runners]
         for gs in runners:
             self._finish(gs, main, deferred_checks)
         return outs
@@ -1008,23 +1075,29 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
             yield i, e, x
 
     def sample_rows_with_attend_and_excite(self, model, x, cond, batch, uc, num_steps=None, init_step=0,
-                                           noise: Optional[torch.Tensor] = None, record_losses: bool = True):
+                                           noise: Optional[torch.Tensor] = None, record_losses: bool = True, char_maps: bool = False):
         """the attend-and-excite sampling loop for a batch of independent images (pipeline.predict_many): the schedule of
         ``_aae_steps`` with the update taken row by row (``attend_and_excite_rows``), and without the per-step VAE decode, the GIF
         and the prints of ``_sample_with_attend_and_excite``.  record_losses: every step emits its attention maps and the per-row
         local loss goes into a device [steps, B] tensor, copied to ``last_row_losses`` once at the end; without it the steps are
-        the fast steps (the latent then differs by the two text-attention forms' rounding)."""
+        the fast steps (the latent then differs by the two text-attention forms' rounding).
+        char_maps: -> (x, maps), the character maps of every row at the middle step (fp32 [B, L, h_map, w_map]): the head and layer
+        mean of the maps that step cached (record_losses), or out of its fused text attention (without)."""
         self._check_fast_path(model)
         require_gpu(x, "EulerEDMSampler.sample_rows_with_attend_and_excite")
         uc = default(uc, cond)
         if noise is None:
             noise = self.draw_step_noise(x.shape, x.device, num_steps, init_step)
         sig, x, stepper = self._begin_loop(model, x, cond, uc, num_steps)
+        mid = char_map_step(len(sig), init_step) if char_maps else -1
+        maps = stepper.new_char_maps() if char_maps else None
         n = max(0, len(sig) - 1 - init_step)
         losses = torch.zeros((n, x.shape[0]), dtype=torch.float32, device=x.device) if record_losses else None
         rows = lambda *a: self.attend_and_excite_rows(*a)[0]
         for k, (i, e, x) in enumerate(self._aae_steps(rows, model, x, cond, batch, sig, init_step, noise)):
-            stepper.step(x, e.sigma, e.sigma_next, emit_maps=record_losses)
+            stepper.step(x, e.sigma, e.sigma_next, emit_maps=record_losses, char_maps=maps if i == mid and not record_losses else None)
+            if record_losses and i == mid:
+                maps.copy_(stepper.unet.char_maps_from_cache(rows_from=x.shape[0] if self._pair else 0))
             if record_losses:
                 losses[k].copy_(model.loss_fn.get_min_local_loss(stepper.unet.attn_map_cache, batch["mask"], batch["seg_mask"],
                                                                  cond_only=self._pair))
@@ -1033,7 +1106,7 @@ class EulerEDMSampler(_PlanSampler, EDMSampler):
         stepper.check()
         if record_losses:
             self.last_row_losses = losses.cpu()
-        return x
+        return (x, maps) if char_maps else x
 
     # ------------------------------------------------------------------------------------------- API step
     def sampler_step(self, sigma, next_sigma, model, x, cond, batch=None, uc=None, gamma=0.0, alpha=0, iter_enabled=False,
