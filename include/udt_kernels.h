@@ -46,6 +46,8 @@
  *                       (test.py:81) + Resize(BICUBIC, antialias=True) + Normalize(0.5, 0.5)  sgm/modules/predictors/model.py:24-29
  *   udt_tattn_fused_maps / udt_resize_bilinear_f32   the per-character attention maps (cfgs.detailed): head mean of the t_attn
  *                       probabilities out of the fused kernel, openaimodel.py:559-591, sampling.py:344-346,380; cv2.resize, demo.py:109
+ *   udt_lpips_input_f32 / udt_conv2d_f32 / udt_maxpool3s2_f32 / udt_lpips_layer_f32
+ *                       lpips.im2tensor + lpips.LPIPS(net='alex').forward on the saved frames  metrics.py:16,24-27 (test.py:94-113,124)
  *   udt_local_loss_maps head-mean + 3x3 blur + masked max of t_attn maps  sgm/modules/diffusionmodules/loss.py:192-235
  *   the reverse pass (round 6; torch.autograd under attend_and_excite, sgm/modules/diffusionmodules/sampling.py:233-252, and under
  *   DiffusionEngine.training_step, sgm/models/diffusion.py:138-172 with loss.py:131-176,237-286):
@@ -787,6 +789,58 @@ int udt_gelu_bwd(const void* a, const void* dy, void* da, int64_t rows, int32_t 
  * Nothing is launched in either case. */
 int udt_ocr_ce_f32(const float* logits, const int32_t* targets, const int32_t* n_chars, const float* weight, float* loss,
                    float* d_logits, int32_t N, int32_t L, int32_t n_cls, int32_t ld, int32_t T, int32_t ld_d, void* stream);
+/* ---- LPIPS (AlexNet) in fp32: the second measurement of the reference's test.py (:122-124, metrics.py:12-30) ------------------------
+ * LAYOUT: every activation of this family is fp32, channels-last: pixel (n, y, x) of a [N, H, W, C] map starts at element
+ * ((n H + y) W + x) ld of its buffer, ld >= C; only the first C elements of a pixel are read or written.  Results are deterministic:
+ * no floating-point atomics, every sum in one fixed order, so they are the same bits from run to run and for every ld.
+ *
+ * udt_conv2d_f32: out = conv(x, w) + bias, ReLU if relu != 0 — square kernel ksize, the same stride and zero padding in both
+ * directions — as an implicit GEMM on v_mfma_f32_32x32x2_f32: rows = the N Ho Wo output pixels, columns = Cout,
+ * K = ksize ksize Cin, Ho = (H + 2 pad - ksize) / stride + 1 (Wo alike).
+ *   x    fp32 [N, H, W, Cin] (ld_x), out fp32 [N, Ho, Wo, Cout] (ld_out); they must not overlap
+ *   w    fp32 [Cout][Kp], packed once per module (packing.pack_conv_f32): column k = (ky ksize + kx) Cin + c holds the checkpoint's
+ *        weight[o, c, ky, kx]; Kp = K rounded up to a multiple of 16, columns K .. Kp - 1 ZERO.  Rows are not padded.
+ *   bias fp32 [Cout] or NULL
+ * Zero padding is produced by the gather: a tap outside the image, and a column k >= K, is a zero that is never loaded.
+ * ROUNDING: out = fp32(acc + bias); the k axis is cut into blocks of 128, each block is one fp32 fused-multiply-add chain in ascending
+ * k starting from 0 (what the MFMA computes: one rounding per term, no wider accumulation), and the blocks' sums are added in ascending
+ * order (blocked summation: the error grows with the block length, not with K); for any K,
+ * |out - exact| <= (K + 2) 2^-24 (sum |w||x| + |bias|) to first order.
+ * UDT_ERR_BAD_ARG: x, w or out NULL.  UDT_ERR_BAD_SHAPE: a count < 1, Cin > 2^20, ld_x < Cin, ld_out < Cout, ksize outside 1 .. 11,
+ * stride outside 1 .. 4, pad outside 0 .. ksize - 1, an image with no output pixel, more than 2^31 - 1 row tiles of 128 pixels,
+ * more than 65535 column tiles of 64 channels (Cout > 4194240).  Nothing is launched or written then. */
+int udt_conv2d_f32(const float* x, const float* w, const float* bias, float* out, int32_t N, int32_t H, int32_t W, int32_t Cin,
+                   int32_t ld_x, int32_t Cout, int32_t ld_out, int32_t ksize, int32_t stride, int32_t pad, int32_t relu, void* stream);
+/* nn.MaxPool2d(3, stride 2) without padding, floor mode, same layout: x [N, H, W, C] (ld_x) -> out [N, (H - 3) / 2 + 1,
+ * (W - 3) / 2 + 1, C] (ld_out).  The maximum starts from the window's first element (all-negative maps are right); no rounding.
+ * A NaN in a window makes that output NaN, as nn.MaxPool2d does; of +0 and -0 the first in row-major window order is kept.
+ * UDT_ERR_BAD_ARG: x or out NULL.  UDT_ERR_BAD_SHAPE: H or W < 3, a count < 1, ld < C, more than 2^38 output elements.
+ * Nothing is launched then. */
+int udt_maxpool3s2_f32(const float* x, float* out, int32_t N, int32_t H, int32_t W, int32_t C, int32_t ld_x, int32_t ld_out,
+                       void* stream);
+/* The network input of N (fake, real) pairs in one launch: samples fp32 [N, 3, H, W] in [0, 1] (the generated frames), images fp32
+ * [N, 3, H, W] in [-1, 1] (batch["image"]), both dense NCHW -> out fp32 [2 N, H, W, 3] (ld_out), frames 0 .. N - 1 from samples,
+ * N .. 2 N - 1 from images.  Per element, every fp32 operation rounded on its own, in this order:
+ *   v = s 255 (samples) or ((x + 1) 0.5) 255 (images): the 8-bit PNG values test.py:94,102,110-113 writes;
+ *   v clamped to [0, 255]; quantise != 0: v = trunc(v) (the PNG's uint8; 0 keeps the continuous value);
+ *   t = fp32(v / 127.5 - 1 evaluated in fp64) (lpips.im2tensor divides a numpy array by a Python float);
+ *   out = (t - shift[c]) / scale[c] (the scaling layer; shift, scale fp32 [3]).
+ * A NaN input gives v = 0 (the clamp drops it).
+ * UDT_ERR_BAD_ARG: a NULL pointer; UDT_ERR_BAD_SHAPE: a count < 1, ld_out < 3, more than 2^38 pixels (2 N H W).  Nothing is
+ * launched then. */
+int udt_lpips_input_f32(const float* samples, const float* images, const float* shift, const float* scale, float* out, int32_t N,
+                        int32_t H, int32_t W, int32_t ld_out, int32_t quantise, void* stream);
+/* One tap of the LPIPS distance: feats fp32 [2 N, P, C] (ld), the features of the stacked frames (pair n = frames n and N + n),
+ * w fp32 [C] (the tap's 1x1 "lin" weights) -> out fp32 [N]: out[n] = (accumulate ? out[n] : 0) + mean over the P pixels of
+ * sum_c w_c (u0_c - u1_c)^2, u = f / (sqrt(sum_c f_c^2) + 1e-10).  A pixel whose features are all zero gives u = 0.
+ * ROUNDING: all fp32, correctly rounded sqrt and divisions; the channel sums over the 64 lanes of a wave, the pixel sum over 16
+ * consecutive pixels per wave, 4 waves per workgroup, one partial per 64 pixels in `scratch`, the partials added per pair in a
+ * fixed order by a second launch.  scratch: the size the query below states for (N, P), written before it is read.
+ * UDT_ERR_BAD_ARG: a NULL pointer; UDT_ERR_BAD_SHAPE: N outside 1 .. 65535, P or C < 1, P above 2^31 - 1 blocks of 64 pixels, ld < C; UDT_ERR_WORKSPACE: scratch_bytes
+ * below the stated size.  Nothing is launched then. */
+size_t udt_lpips_layer_scratch_bytes(int32_t N, int64_t P);
+int udt_lpips_layer_f32(const float* feats, const float* w, float* out, int32_t N, int64_t P, int32_t C, int32_t ld, int32_t accumulate,
+                        void* scratch, size_t scratch_bytes, void* stream);
 /* x bf16 += y bf16 (n elements, n % 8 == 0) ; utility for residuals outside GEMM epilogues */
 int udt_add_bf16(void* x, const void* y, int64_t n, void* stream);
 

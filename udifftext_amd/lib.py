@@ -187,6 +187,11 @@ SYMBOLS = {
     "udt_ln_param_grad_acc": (C.c_int, [_vp, _vp, _fp, _fp, _i64, _i32, _f32, _i32, _vp]),
     "udt_bucket_update_f32": (C.c_int, [_vp, _vp, _i32, _fp, _fp, _fp, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _vp]),
     "udt_bucket_swap_f32": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "udt_conv2d_f32": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "udt_maxpool3s2_f32": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "udt_lpips_input_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "udt_lpips_layer_scratch_bytes": (C.c_size_t, [_i32, _i64]),
+    "udt_lpips_layer_f32": (C.c_int, [_fp, _fp, _fp, _i32, _i64, _i32, _i32, _i32, _vp, C.c_size_t, _vp]),
     "udt_add_bf16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "udt_debug_set": (C.c_int, [C.c_char_p, _i32]),
     "udt_bias_add_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),

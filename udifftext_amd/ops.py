@@ -1022,6 +1022,92 @@ def resize_bilinear(x: torch.Tensor, out_hw, out: Optional[torch.Tensor] = None)
     return out
 
 
+# ---- LPIPS (csrc/lpips.hip): fp32 channels-last maps [N, H, W, C] whose pixels are dense and whose pixel stride (ld) is >= C
+def _nhwc_f32(t: torch.Tensor) -> int:
+    """the ld of a channels-last fp32 map (pixels dense in (n, y, x) order), checked"""
+    assert t.dtype == torch.float32 and t.dim() == 4 and t.stride(3) == 1
+    N, H, W_, Cc = t.shape
+    # (the stride of a dimension of size 1 says nothing: the ld is read off the dimensions that do step)
+    lds = {t.stride(d) // step if t.stride(d) % step == 0 else -1 for d, size, step in ((0, N, H * W_), (1, H, W_), (2, W_, 1)) if size > 1}
+    ld = lds.pop() if lds else Cc
+    assert not lds and ld >= Cc, (tuple(t.shape), t.stride())
+    return ld
+
+
+def conv2d_f32(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], cout: int, ksize: int, stride: int, pad: int,
+               relu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 convolution + bias (+ ReLU) on f32-input MFMA (udt_conv2d_f32): x fp32 [N, H, W, Cin] channels-last, w the packed
+    [cout, Kp] weights of ``packing.pack_conv_f32`` -> fp32 [N, Ho, Wo, cout].  A geometry the kernel refuses raises ValueError."""
+    N, H, W_, Cin = x.shape
+    ldx = _nhwc_f32(x)
+    kp = (ksize * ksize * Cin + 15) // 16 * 16
+    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (cout, kp), (tuple(w.shape), (cout, kp))
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout)
+    Ho, Wo = conv_out_hw(H, W_, ksize, max(1, stride), (pad, pad))
+    if out is None:
+        if Ho < 1 or Wo < 1:
+            raise ValueError(f"conv2d_f32: a {H} x {W_} map has no output pixel under kernel {ksize}, stride {stride}, padding {pad}")
+        out = torch.empty((N, Ho, Wo, cout), dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == (N, Ho, Wo, cout) and out.device == x.device
+    L.check(L.load().udt_conv2d_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), N, H, W_, Cin, ldx, cout, _nhwc_f32(out), ksize, stride, pad,
+                                    int(relu), _stream()), "udt_conv2d_f32")
+    return out
+
+
+def maxpool3s2_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.MaxPool2d(3, 2) (no padding, floor) of a channels-last fp32 map (udt_maxpool3s2_f32)"""
+    N, H, W_, Cc = x.shape
+    ldx = _nhwc_f32(x)
+    if H < 3 or W_ < 3:
+        raise ValueError(f"maxpool3s2_f32: a {H} x {W_} map has no 3 x 3 window")
+    shape = (N, (H - 3) // 2 + 1, (W_ - 3) // 2 + 1, Cc)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == shape and out.device == x.device
+    L.check(L.load().udt_maxpool3s2_f32(_ptr(x), _ptr(out), N, H, W_, Cc, ldx, _nhwc_f32(out), _stream()), "udt_maxpool3s2_f32")
+    return out
+
+
+def lpips_input(samples: torch.Tensor, images: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, quantise: bool = True,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the LPIPS network input of N pairs in one launch (udt_lpips_input_f32): samples fp32 [N, 3, H, W] in [0, 1], images fp32
+    [N, 3, H, W] in [-1, 1] -> fp32 [2 N, H, W, 3] channels-last, the samples' frames first"""
+    for t in (samples, images):
+        assert t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == 3 and t.is_contiguous()
+    assert samples.shape == images.shape and samples.device == images.device
+    for t in (shift, scale):
+        assert t.dtype == torch.float32 and t.numel() == 3 and t.is_contiguous() and t.device == samples.device
+    N, _, H, W_ = samples.shape
+    if out is None:
+        out = torch.empty((2 * N, H, W_, 3), dtype=torch.float32, device=samples.device)
+    assert tuple(out.shape) == (2 * N, H, W_, 3) and out.device == samples.device
+    L.check(L.load().udt_lpips_input_f32(_ptr(samples), _ptr(images), _ptr(shift), _ptr(scale), _ptr(out), N, H, W_, _nhwc_f32(out),
+                                         int(bool(quantise)), _stream()), "udt_lpips_input_f32")
+    return out
+
+
+def lpips_layer_scratch_bytes(n_pairs: int, pixels: int) -> int:
+    return int(L.load().udt_lpips_layer_scratch_bytes(int(n_pairs), int(pixels)))
+
+
+def lpips_layer(feats: torch.Tensor, w: torch.Tensor, out: torch.Tensor, accumulate: bool, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """one tap of the LPIPS distance (udt_lpips_layer_f32): feats fp32 [2 N, h, w, C] channels-last (pair n = frames n and N + n),
+    w fp32 [C] -> out fp32 [N], overwritten or (``accumulate``) added to.  ``scratch``: uint8, at least ``lpips_layer_scratch_bytes``."""
+    N2, h, w_, Cc = feats.shape
+    ld = _nhwc_f32(feats)
+    assert N2 % 2 == 0 and N2 > 0
+    N, P = N2 // 2, h * w_
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.numel() == Cc and w.device == feats.device
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == N and out.device == feats.device
+    need = lpips_layer_scratch_bytes(N, P)
+    if scratch is None:
+        scratch = torch.empty((need,), dtype=torch.uint8, device=feats.device)
+    assert scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.device == feats.device
+    L.check(L.load().udt_lpips_layer_f32(_ptr(feats), _ptr(w), _ptr(out), N, P, Cc, ld, int(bool(accumulate)), _ptr(scratch),
+                                         scratch.numel(), _stream()), "udt_lpips_layer_f32")
+    return out
+
+
 def crop_resize_aa_bwd(d_out: torch.Tensor, boxes: torch.Tensor, img_shape, mul: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """the adjoint of ``crop_resize_aa`` (udt_crop_resize_aa_bwd_f32): d_out fp32 [N, C, oh, ow], the same DEVICE int32 boxes [N, 5]
     -> d_img fp32 ``img_shape`` = [B, C, H, W], every element written (zero outside the boxes and for images without one).

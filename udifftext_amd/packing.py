@@ -58,6 +58,19 @@ def pack_conv(w: torch.Tensor, segments=None, n_pad_to: int = 4) -> torch.Tensor
     return out.reshape(Np, -1).contiguous()
 
 
+F32_KPAD = 16           # K elements per chunk of the fp32 convolution (csrc/lpips.hip)
+
+
+def pack_conv_f32(w: torch.Tensor) -> torch.Tensor:
+    """[N, Cin, kh, kw] fp32 -> fp32 [N, Kp] for udt_conv2d_f32: k = (ky*kw + kx)*Cin + c, K = kh*kw*Cin padded with zeros to a
+    multiple of 16.  The values are the checkpoint's, unrounded; rows are not padded."""
+    N, Cin, kh, kw = w.shape
+    K = kh * kw * Cin
+    out = torch.zeros((N, _round_up(K, F32_KPAD)), dtype=torch.float32, device=w.device)
+    out[:, :K] = w.float().permute(0, 2, 3, 1).reshape(N, K)
+    return out.contiguous()
+
+
 # output row parity a (column parity b) -> the 3x3 taps dy (dx) that land on low-resolution row i - 1 + a + r, r = 0, 1
 UP4_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
 

@@ -390,10 +390,72 @@ def _host_boxes(batch: dict, k: int):
     return labels, rb
 
 
+def _lpips_shapes(batches, lpips) -> None:
+    """host check of ``lpips_of``'s inputs before anything is sampled: every batch has a [B, 3, H, W] image large enough for the taps"""
+    for k, batch in enumerate(batches):
+        img = batch.get("image")
+        if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError(f"batch {k} has no [B, 3, H, W] image: LPIPS compares every generated frame with it")
+        if hasattr(lpips, "map_sizes"):                    # (ValueError: a frame too small for the module's taps)
+            lpips.map_sizes(*img.shape[-2:])
+
+
+@torch.no_grad()
+def lpips_of(outputs, batches, lpips, chunk: int = 32) -> list:
+    """LPIPS of every generated frame against the image it was made from (reference metrics.py:12-30 on the frames test.py saves):
+    ``outputs`` is ``predict_many``'s list (only the samples are read), ``batches`` the batches it was given (their ``image``,
+    [-1, 1]); ``lpips(samples, images) -> [n]`` is called on chunks of at most ``chunk`` consecutive pairs of one image size — a
+    chunk may span batches, and ends where the size changes.  Nothing synchronises per image: the chunks' results stay on the device
+    and ONE device-to-host copy at the end brings them back.  -> per batch, in input order, a list of floats.
+    Per image, not per width-concatenated batch: see udifftext_amd/lpips_alex.py."""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk must be a positive count, not {chunk!r}")
+    if len(outputs) != len(batches):
+        raise ValueError(f"{len(outputs)} outputs for {len(batches)} batches")
+    vals, cur_s, cur_i, hw, count = [], [], [], None, 0
+
+    def flush():
+        nonlocal count
+        if cur_s:
+            vals.append(lpips(torch.cat(cur_s, 0) if len(cur_s) > 1 else cur_s[0], torch.cat(cur_i, 0) if len(cur_i) > 1 else cur_i[0]))
+        cur_s.clear()
+        cur_i.clear()
+        count = 0
+
+    for k, (o, b) in enumerate(zip(outputs, batches)):
+        s, im = o[0], b["image"]
+        if tuple(s.shape) != tuple(im.shape):
+            raise ValueError(f"batch {k}: samples {tuple(s.shape)} and image {tuple(im.shape)} differ in shape")
+        if hw is not None and tuple(s.shape[-2:]) != hw:
+            flush()
+        hw = tuple(s.shape[-2:])
+        im = im.to(s.device, non_blocking=True)
+        i = 0
+        while i < s.shape[0]:
+            take = min(chunk - count, s.shape[0] - i)
+            cur_s.append(s[i:i + take])
+            cur_i.append(im[i:i + take])
+            count += take
+            i += take
+            if count == chunk:
+                flush()
+    flush()
+    flat = torch.cat([v.reshape(-1).float() for v in vals]).cpu().tolist() if vals else []
+    per, o = [], 0
+    for out in outputs:
+        n = int(out[0].shape[0])
+        per.append(flat[o:o + n])
+        o += n
+    if o != len(flat):
+        raise RuntimeError(f"the LPIPS module returned {len(flat)} values for {o} pairs")
+    return per
+
+
 @torch.no_grad()
 def evaluate(cfgs, model, sampler, batches, predictor, device: Optional[torch.device] = None, in_flight: Optional[int] = None,
              fuse: Optional[int] = None, image_seeds: Optional[list] = None, ocr_batch: Optional[int] = 64,
-             return_samples: bool = False) -> dict:
+             return_samples: bool = False, lpips=None, lpips_chunk: int = 32) -> dict:
     """reference test.py:74-91 in throughput mode: generate with ``predict_many``, read the text back with the OCR predictor, count
     the exact matches — the sequence accuracy UDiffText is judged by.
     Every batch carries ``label`` (one string per image) and ``r_bbox`` ([B, 4] host integers: top, bottom, left, right of the text
@@ -406,9 +468,17 @@ def evaluate(cfgs, model, sampler, batches, predictor, device: Optional[torch.de
     pred.lower() == label.lower() (test.py:84).
     -> {"accuracy", "correct", "total", "pred": [[str]], "label": [[str]]} (per batch, input order) and, with ``return_samples``,
     "outputs": the ``predict_many`` list.  ``predictor`` is duck-typed: only ``transform_boxes`` and ``txt_of`` are used.
-    One device only: under data parallelism each rank calls ``evaluate`` on its shard and the ranks add up "correct" and "total"."""
+    One device only: under data parallelism each rank calls ``evaluate`` on its shard and the ranks add up "correct" and "total".
+    ``lpips`` (a ``udifftext_amd.lpips_alex.LPIPS``, or anything callable as lpips(samples, images) -> [n]): the reference's second
+    measurement (test.py:122-124) on the same frames — the result also carries "lpips" (the mean over all images), "lpips_sum"
+    (ranks add "lpips_sum" and "total") and "lpips_per_image" (per batch, input order), from ``lpips_of`` in chunks of
+    ``lpips_chunk`` pairs.  Without it nothing changes: the same keys, the same launches, the same samples."""
     if ocr_batch is not None and int(ocr_batch) < 1:
         raise ValueError(f"ocr_batch must be a positive count or None, not {ocr_batch!r}")
+    if lpips is not None:
+        if int(lpips_chunk) < 1:
+            raise ValueError(f"lpips_chunk must be a positive count, not {lpips_chunk!r}")
+        _lpips_shapes(batches, lpips)
     labels, boxes = [], []
     for k, batch in enumerate(batches):
         lb, rb = _host_boxes(batch, k)
@@ -432,6 +502,11 @@ def evaluate(cfgs, model, sampler, batches, predictor, device: Optional[torch.de
         o += len(lb)
     correct = sum(p.lower() == t.lower() for ps, ls in zip(pred, labels) for p, t in zip(ps, ls))
     res = {"accuracy": correct / total if total else 0.0, "correct": int(correct), "total": int(total), "pred": pred, "label": labels}
+    if lpips is not None:
+        per = lpips_of(outputs, batches, lpips, chunk=lpips_chunk)
+        res["lpips_per_image"] = per
+        res["lpips_sum"] = float(sum(v for vs in per for v in vs))
+        res["lpips"] = res["lpips_sum"] / total if total else 0.0
     if return_samples:
         res["outputs"] = outputs
     return res
