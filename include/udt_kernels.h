@@ -382,7 +382,9 @@ int udt_gn_stats(const void* x, const void* x2, float* partials, int32_t B, int6
                  int32_t G, void* stream);
 /* y = act((x - mean) * rstd * gamma + beta); act: 0 none, 1 SiLU.  y may alias x when x2 == NULL.
  * x2 (optional, C2 channels) is a second NHWC source concatenated after x's C channels (UNet skip concat,
- * openaimodel.py:620); statistics and output cover the C + C2 concatenated channels, y is [B, HW, C + C2]. */
+ * openaimodel.py:620); statistics and output cover the C + C2 concatenated channels, y is [B, HW, C + C2].
+ * udt_gn_apply also requires G <= 256 and 256 % G == 0 (its 256 threads combine the chunk partials as G groups x 256 / G lanes);
+ * both require C + C2 <= 4096. */
 int udt_gn_apply(const void* x, const void* x2, void* y, const float* partials, const float* gamma,
                  const float* beta, int32_t B, int64_t HW, int32_t C, int32_t C2, int32_t G, float eps, int32_t act,
                  void* stream);
@@ -398,7 +400,8 @@ int udt_gn_strip(const void* x, const void* x2, void* y, const float* gamma, con
  *   the layer(s) that produced the input; slotsN = slots per sample.  Groups run over the C1 + C2 concatenated channels.
  *   scsh out fp32 [B][(C1+C2)/64][2][64]: chunk-blocked (scale of 64 channels, then their shift) — the layout the
  *   convolution's LDS-DMA reads.  scale = rstd * gamma, shift = beta - mean * scale; fp32 partials, fp64 combine.
- *   (C1 + C2) % 64 == 0, (C1 + C2) % G == 0. */
+ *   (C1 + C2) % 64 == 0, (C1 + C2) % G == 0, G <= 256, (C1 + C2) / G <= 128 (one workgroup of 256 threads per (sample, group):
+ *   256 / ((C1 + C2) / G) slot lanes per channel). */
 int udt_gn_finalize(const float* stats1, int32_t slots1, int32_t C1, const float* stats2, int32_t slots2, int32_t C2,
                     const float* gamma, const float* beta, float* scsh, int32_t B, int64_t HW, int32_t G, float eps,
                     void* stream);

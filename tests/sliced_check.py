@@ -81,6 +81,13 @@ def gn_group_slices(B, C, groups):
             yield (b, slice(None), slice(g * cpg, (g + 1) * cpg))
 
 
+def gn_strip_slices(B, C, cw):
+    """[B, HW, C]: (sample, strip of cw channels) — the gw consecutive groups one workgroup of the forward strip GroupNorm owns"""
+    for b in range(B):
+        for c0 in range(0, C, cw):
+            yield (b, slice(None), slice(c0, c0 + cw))
+
+
 def flat_slices(B, per_sample, step):
     """[B, per_sample] (a flattened sample): consecutive spans of ``step`` elements — GroupNorm backward's apply workgroup takes
     1024 16-byte pieces = 8192 elements"""
