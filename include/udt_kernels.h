@@ -48,6 +48,8 @@
  *                       probabilities out of the fused kernel, openaimodel.py:559-591, sampling.py:344-346,380; cv2.resize, demo.py:109
  *   udt_lpips_input_f32 / udt_conv2d_f32 / udt_maxpool3s2_f32 / udt_lpips_layer_f32
  *                       lpips.im2tensor + lpips.LPIPS(net='alex').forward on the saved frames  metrics.py:16,24-27 (test.py:94-113,124)
+ *   udt_fid_input_f32 / udt_conv2d_rect_f32 / udt_pool3_f32 / udt_mean_pixels_f32 / udt_moments_accum_f64
+ *                       pytorch_fid's InceptionV3 pool features and their mean / covariance  metrics.py:5-10 (test.py:119-121)
  *   udt_local_loss_maps head-mean + 3x3 blur + masked max of t_attn maps  sgm/modules/diffusionmodules/loss.py:192-235
  *   the reverse pass (round 6; torch.autograd under attend_and_excite, sgm/modules/diffusionmodules/sampling.py:233-252, and under
  *   DiffusionEngine.training_step, sgm/models/diffusion.py:138-172 with loss.py:131-176,237-286):
@@ -844,6 +846,56 @@ int udt_lpips_input_f32(const float* samples, const float* images, const float* 
 size_t udt_lpips_layer_scratch_bytes(int32_t N, int64_t P);
 int udt_lpips_layer_f32(const float* feats, const float* w, float* out, int32_t N, int64_t P, int32_t C, int32_t ld, int32_t accumulate,
                         void* scratch, size_t scratch_bytes, void* stream);
+/* ---- FID (InceptionV3 pool features) in fp32 + fp64 moments: the third measurement of the reference's test.py (:119-121,
+ * metrics.py:5-10) — csrc/fid.hip.  Same activation family and LAYOUT as LPIPS above: fp32 channels-last [N, H, W, C] with a pixel
+ * stride ld >= C.  A channel slice of a wider map is (pointer + first channel, ld of the wide map): Inception's concatenations are
+ * written and read that way, no copy.  Deterministic: no floating-point atomics, every sum in one fixed order, the same bits for every
+ * ld and every run.
+ *
+ * udt_conv2d_rect_f32: udt_conv2d_f32 with a kh x kw kernel and a zero padding per axis: k = (ky kw + kx) Cin + c,
+ * K = kh kw Cin, Ho = (H + 2 pad_h - kh) / stride + 1, Wo = (W + 2 pad_w - kw) / stride + 1; w fp32 [Cout][Kp] from
+ * packing.pack_conv_f32 of a [Cout, Cin, kh, kw] weight.  It is the same kernel (csrc/conv_f32.h): operands, ROUNDING (blocks of 128 k)
+ * and bound are those stated for udt_conv2d_f32, and kh == kw, pad_h == pad_w gives udt_conv2d_f32's bits.
+ * UDT_ERR_BAD_ARG: x, w or out NULL.  UDT_ERR_BAD_SHAPE: a count < 1, Cin > 2^20, ld_x < Cin, ld_out < Cout, kh or kw outside 1 .. 11,
+ * stride outside 1 .. 4, pad_h outside 0 .. kh - 1, pad_w outside 0 .. kw - 1, an image with no output pixel, the grid limits of
+ * udt_conv2d_f32.  Nothing is launched or written then. */
+int udt_conv2d_rect_f32(const float* x, const float* w, const float* bias, float* out, int32_t N, int32_t H, int32_t W, int32_t Cin,
+                        int32_t ld_x, int32_t Cout, int32_t ld_out, int32_t kh, int32_t kw, int32_t stride, int32_t pad_h, int32_t pad_w,
+                        int32_t relu, void* stream);
+/* 3 x 3 pool, stride 1 or 2, padding 0 or 1, floor mode: x [N, H, W, C] (ld_x) -> out [N, (H + 2 pad - 3) / stride + 1,
+ * (W + 2 pad - 3) / stride + 1, C] (ld_out).  Only the taps inside the image take part, in row-major window order.
+ *   average == 0: the maximum (nn.MaxPool2d: padding never wins); a NaN in a window makes that output NaN; of +0 and -0 the first is
+ *     kept; no rounding.  stride 2, pad 0 gives udt_maxpool3s2_f32's bits.
+ *   average != 0: F.avg_pool2d(count_include_pad=False): the fp32 sum of the taps inside the image, added one by one starting from 0,
+ *     divided by their number (1 .. 9) — at most eight rounded additions and one correctly rounded division.
+ * UDT_ERR_BAD_ARG: x or out NULL.  UDT_ERR_BAD_SHAPE: a count < 1, ld < C, stride outside 1 .. 2, pad outside 0 .. 1, H + 2 pad < 3 or
+ * W + 2 pad < 3, more than 2^38 output elements.  Nothing is launched then. */
+int udt_pool3_f32(const float* x, float* out, int32_t N, int32_t H, int32_t W, int32_t C, int32_t ld_x, int32_t ld_out, int32_t stride,
+                  int32_t pad, int32_t average, void* stream);
+/* The Inception input of N (fake, real) pairs in one launch: samples fp32 [N, 3, H, W] in [0, 1], images fp32 [N, 3, H, W] in
+ * [-1, 1], dense NCHW -> out fp32 [2 N, size, size, 3] (ld_out), frames 0 .. N - 1 from samples, N .. 2 N - 1 from images
+ * (size = 299 for FID).  Per source element, every fp32 operation rounded on its own:
+ *   v = s 255 (samples) or ((x + 1) 0.5) 255 (images), clamped to [0, 255]; quantise != 0: v = trunc(v) (the saved PNG's uint8);
+ *   p = v / 255 (ToTensor), correctly rounded.
+ * Then F.interpolate(size, mode="bilinear", align_corners=False) of p with udt_resize_bilinear_f32's coordinate rule and ROUNDING
+ * (exact taps, weights rounded once, top = fma(wx1, p[i0y][i1x], wx0 p[i0y][i0x]), bot alike, r = fma(wy1, bot, wy0 top)), and
+ * out = 2 r - 1 (2 r exact, one rounding).  A NaN input gives v = 0.  Any H, W >= 1.
+ * UDT_ERR_BAD_ARG: a NULL pointer; UDT_ERR_BAD_SHAPE: a count < 1, size > 4096, ld_out < 3, more than 2^38 output pixels.  Nothing is
+ * launched then. */
+int udt_fid_input_f32(const float* samples, const float* images, float* out, int32_t N, int32_t H, int32_t W, int32_t size,
+                      int32_t ld_out, int32_t quantise, void* stream);
+/* Global average pool: x fp32 [N, P, C] (pixel stride ld_x) -> out fp32 [N, C] (row stride ld_out): the P pixels added in ascending
+ * order starting from 0 (P rounded additions), then one correctly rounded division by P.
+ * UDT_ERR_BAD_ARG: a NULL pointer; UDT_ERR_BAD_SHAPE: a count < 1, P > 2^24, ld < C.  Nothing is launched then. */
+int udt_mean_pixels_f32(const float* x, float* out, int32_t N, int64_t P, int32_t C, int32_t ld_x, int32_t ld_out, void* stream);
+/* Streaming first and second moments: x fp32 [n, D] (row stride ld) -> sum fp64 [D] += sum_r x_r, outer fp64 [D, D] (dense) += X^T X.
+ * Every fp32 value is converted exactly to fp64; the contraction over the rows runs on v_mfma_f64_16x16x4_f64 (fp64 fused
+ * multiply-adds, rows in ascending order, four per instruction), starting from 0, and the launch's total is added to the stored value
+ * once: |outer_ij - exact| <= n 2^-53 sum_r |x_ri x_rj| + 2^-53 |stored result| to first order; integer data below 2^53 is exact.
+ * The FULL matrix is computed (no mirrored triangle); each output element belongs to one wave; sum is added by the waves of the first
+ * tile column.  sum and outer must not overlap x; any D >= 1, n >= 1.
+ * UDT_ERR_BAD_ARG: a NULL pointer; UDT_ERR_BAD_SHAPE: n < 1, D < 1, D > 2^18, ld < D.  Nothing is launched or written then. */
+int udt_moments_accum_f64(const float* x, double* sum, double* outer, int32_t n, int32_t D, int32_t ld, void* stream);
 /* x bf16 += y bf16 (n elements, n % 8 == 0) ; utility for residuals outside GEMM epilogues */
 int udt_add_bf16(void* x, const void* y, int64_t n, void* stream);
 

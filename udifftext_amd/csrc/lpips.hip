@@ -5,10 +5,12 @@
 // Nothing here uses a floating-point atomic: every sum has one fixed order, so a result depends on the values alone — not on the
 // run, not on the leading dimensions.
 #include "common.h"
+#include "conv_f32.h"
 
 namespace {
 
-// ---- udt_conv2d_f32: implicit GEMM, rows = output pixels (n, oy, ox), columns = output channels, k = (ky ks + kx) Cin + c ---------
+// ---- udt_conv2d_f32 / udt_conv2d_rect_f32: implicit GEMM, rows = output pixels (n, oy, ox), columns = output channels,
+// k = (ky kw + kx) Cin + c (conv_f32.h: one kernel behind both entry points) -------------------------------------------------------
 // A 256-thread workgroup owns a 128-pixel x 64-channel tile; wave w owns pixels 32 w .. 32 w + 31 and all 64 channels in two
 // v_mfma_f32_32x32x2_f32 accumulators (one wave per SIMD; the instruction's dependent latency equals its issue interval, so the
 // accumulator count does not bound the issue rate).  What bounds this kernel is its LDS staging — one buffer and two barriers per
@@ -16,16 +18,12 @@ namespace {
 // rows and 4 weight rows t / 16 + 16 i into registers while the previous chunk is multiplied, then the tile goes through LDS as
 // [k][row].  A tap outside the image, a pixel row >= M, a weight row >= Cout and a k >= K contribute a ZERO that is produced here:
 // no address outside the operands is formed into a load.
-constexpr int CV_BM = 128, CV_BN = 64, CV_BK = 16;
+constexpr int CV_BM = udt_conv_f32::BM, CV_BN = udt_conv_f32::BN, CV_BK = udt_conv_f32::BK;
 constexpr int CV_LDA = CV_BM + 4, CV_LDB = CV_BN + 4;      // (+4: the 16 x 4 (k, row) pairs a wave writes at once fall into 64 distinct banks)
 constexpr int CV_FLUSH = 8;                                // chunks per fused-multiply-add chain: 128 k, then the chain is added to the total
 constexpr int CV_NOWHERE = -(1 << 28);                     // iy0 / ix0 of a pixel row >= M: no tap of it is inside any image
 
-struct ConvParams {
-  const float* x; const float* w; const float* bias; float* out;
-  int H, W, Cin, ldx, Cout, ldo, ks, stride, pad, relu, Ho, Wo, K, Kp;
-  long long M;
-};
+using ConvParams = udt_conv_f32::Params;
 
 __global__ void __launch_bounds__(256) conv2d_f32_kernel(const ConvParams p) {
   __shared__ float As[CV_BK * CV_LDA];
@@ -45,8 +43,8 @@ __global__ void __launch_bounds__(256) conv2d_f32_kernel(const ConvParams p) {
       const long long t = m / p.Wo;
       const int oy = (int)(t % p.Ho);
       const long long n = t / p.Ho;
-      iy0[i] = oy * p.stride - p.pad;
-      ix0[i] = ox * p.stride - p.pad;
+      iy0[i] = oy * p.stride - p.pad_h;
+      ix0[i] = ox * p.stride - p.pad_w;
       pix[i] = (n * p.H + iy0[i]) * p.W + ix0[i];
     } else {
       iy0[i] = ix0[i] = CV_NOWHERE;
@@ -59,7 +57,7 @@ __global__ void __launch_bounds__(256) conv2d_f32_kernel(const ConvParams p) {
     const int k = chunk * CV_BK + kk;
     const bool k_ok = k < p.K;
     const int tap = k / p.Cin, ch = k - tap * p.Cin;
-    const int ky = tap / p.ks, kx = tap - ky * p.ks;
+    const int ky = tap / p.kw, kx = tap - ky * p.kw;
     const long long koff = (long long)ky * p.W + kx;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -223,6 +221,20 @@ long long lpips_layer_blocks(long long P) { return (P + LP_PIX - 1) / LP_PIX; }
 
 }  // namespace
 
+int udt_conv_f32::launch(Params& p, hipStream_t s) {
+  p.Ho = (p.H + 2 * p.pad_h - p.kh) / p.stride + 1;
+  p.Wo = (p.W + 2 * p.pad_w - p.kw) / p.stride + 1;
+  p.K = p.kh * p.kw * p.Cin;
+  p.Kp = (p.K + CV_BK - 1) / CV_BK * CV_BK;
+  p.M = (long long)p.N * p.Ho * p.Wo;
+  const long long mt = (p.M + CV_BM - 1) / CV_BM, nt = (p.Cout + CV_BN - 1) / CV_BN;
+  if (mt > 0x7fffffffLL || nt > 65535) return UDT_ERR_BAD_SHAPE;                            // grid limits
+  UdtProfScope prof(0, s);
+  hipLaunchKernelGGL(conv2d_f32_kernel, dim3((unsigned)mt, (unsigned)nt), dim3(256), 0, s, p);
+  UDT_CHECK_LAUNCH();
+  return UDT_OK;
+}
+
 extern "C" int udt_conv2d_f32(const float* x, const float* w, const float* bias, float* out, int32_t N, int32_t H, int32_t W, int32_t Cin,
                               int32_t ld_x, int32_t Cout, int32_t ld_out, int32_t ksize, int32_t stride, int32_t pad, int32_t relu,
                               void* stream) {
@@ -232,19 +244,9 @@ extern "C" int udt_conv2d_f32(const float* x, const float* w, const float* bias,
   if (H + 2 * pad < ksize || W + 2 * pad < ksize) return UDT_ERR_BAD_SHAPE;                 // no output pixel
   ConvParams p;
   p.x = x; p.w = w; p.bias = bias; p.out = out;
-  p.H = H; p.W = W; p.Cin = Cin; p.ldx = ld_x; p.Cout = Cout; p.ldo = ld_out; p.ks = ksize; p.stride = stride; p.pad = pad; p.relu = relu != 0;
-  p.Ho = (H + 2 * pad - ksize) / stride + 1;
-  p.Wo = (W + 2 * pad - ksize) / stride + 1;
-  p.K = ksize * ksize * Cin;
-  p.Kp = (p.K + CV_BK - 1) / CV_BK * CV_BK;
-  p.M = (long long)N * p.Ho * p.Wo;
-  const long long mt = (p.M + CV_BM - 1) / CV_BM, nt = (Cout + CV_BN - 1) / CV_BN;
-  if (mt > 0x7fffffffLL || nt > 65535) return UDT_ERR_BAD_SHAPE;                            // grid limits
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  UdtProfScope prof(0, s);
-  hipLaunchKernelGGL(conv2d_f32_kernel, dim3((unsigned)mt, (unsigned)nt), dim3(256), 0, s, p);
-  UDT_CHECK_LAUNCH();
-  return UDT_OK;
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.ldx = ld_x; p.Cout = Cout; p.ldo = ld_out; p.kh = p.kw = ksize; p.stride = stride;
+  p.pad_h = p.pad_w = pad; p.relu = relu != 0;
+  return udt_conv_f32::launch(p, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int udt_maxpool3s2_f32(const float* x, float* out, int32_t N, int32_t H, int32_t W, int32_t C, int32_t ld_x, int32_t ld_out,

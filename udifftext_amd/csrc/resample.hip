@@ -16,6 +16,7 @@
 // cancellation error, times the cubic's slope, is larger than the whole fp32 accumulation error); the normalised weight is rounded to
 // fp32 once, and products and sums are fp32.  A weight is evaluated once per 8 rows (horizontal) / once per tap (vertical).
 #include "common.h"
+#include "bilinear.h"
 
 namespace {
 
@@ -234,19 +235,7 @@ __global__ void __launch_bounds__(RB_COLS) crop_resize_aa_bwd_kernel(const float
 // ---- bilinear resize of fp32 planes (the character maps at image size: demo.py:109 cv2.resize, F.interpolate(mode="bilinear",
 // align_corners=False)).  Half-pixel centres, edge clamp: output i reads source coordinate ((2 i + 1) n_in - n_out) / (2 n_out),
 // clamped below at 0 — kept as that integer fraction, so the two taps are exact and the weights are the fraction rounded to fp32 once.
-struct BlTap { int i0, i1; float w0, w1; };
-UDT_DEVINL BlTap bl_tap(int i, int n_in, int n_out) {
-  const long long den = 2LL * n_out;
-  long long num = (2LL * i + 1) * n_in - n_out;
-  if (num < 0) num = 0;
-  const long long q = num / den, r = num - q * den;
-  BlTap t;
-  t.i0 = (int)min(q, (long long)(n_in - 1));
-  t.i1 = min(t.i0 + 1, n_in - 1);
-  t.w1 = (float)((double)r / (double)den);
-  t.w0 = (float)((double)(den - r) / (double)den);
-  return t;
-}
+// (BlTap, bl_tap: bilinear.h, shared with the FID input stage)
 // one thread per output element, x fastest
 __global__ void __launch_bounds__(256) resize_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, long long total,
                                                               int h, int w, int H, int W) {

@@ -192,6 +192,11 @@ SYMBOLS = {
     "udt_lpips_input_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "udt_lpips_layer_scratch_bytes": (C.c_size_t, [_i32, _i64]),
     "udt_lpips_layer_f32": (C.c_int, [_fp, _fp, _fp, _i32, _i64, _i32, _i32, _i32, _vp, C.c_size_t, _vp]),
+    "udt_conv2d_rect_f32": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "udt_pool3_f32": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "udt_fid_input_f32": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "udt_mean_pixels_f32": (C.c_int, [_fp, _fp, _i32, _i64, _i32, _i32, _i32, _vp]),
+    "udt_moments_accum_f64": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _vp]),
     "udt_add_bf16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "udt_debug_set": (C.c_int, [C.c_char_p, _i32]),
     "udt_bias_add_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),

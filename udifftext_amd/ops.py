@@ -1108,6 +1108,89 @@ def lpips_layer(feats: torch.Tensor, w: torch.Tensor, out: torch.Tensor, accumul
     return out
 
 
+# ---- FID (csrc/fid.hip): the same fp32 channels-last family; a channel slice t[..., a:b] of a wider map is a valid operand and output
+def conv2d_rect_f32(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], cout: int, kernel, stride: int, pad,
+                    relu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``conv2d_f32`` with kernel = (kh, kw) and pad = (pad_h, pad_w) (udt_conv2d_rect_f32); x and ``out`` may be channel slices"""
+    N, H, W_, Cin = x.shape
+    ldx = _nhwc_f32(x)
+    (kh, kw), (ph, pw) = (int(v) for v in kernel), (int(v) for v in pad)
+    kp = (kh * kw * Cin + 15) // 16 * 16
+    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (cout, kp), (tuple(w.shape), (cout, kp))
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout)
+    s = max(1, stride)
+    Ho, Wo = (H + 2 * ph - kh) // s + 1, (W_ + 2 * pw - kw) // s + 1
+    if out is None:
+        if Ho < 1 or Wo < 1:
+            raise ValueError(f"conv2d_rect_f32: a {H} x {W_} map has no output pixel under kernel {kh} x {kw}, stride {stride}, "
+                             f"padding ({ph}, {pw})")
+        out = torch.empty((N, Ho, Wo, cout), dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == (N, Ho, Wo, cout) and out.device == x.device
+    L.check(L.load().udt_conv2d_rect_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), N, H, W_, Cin, ldx, cout, _nhwc_f32(out), kh, kw, stride,
+                                         ph, pw, int(relu), _stream()), "udt_conv2d_rect_f32")
+    return out
+
+
+def pool3_f32(x: torch.Tensor, stride: int, pad: int, average: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3 x 3 max-pool, or the average that does not count padding (F.avg_pool2d(count_include_pad=False)), stride 1 or 2, padding 0
+    or 1, floor mode, of a channels-last fp32 map (udt_pool3_f32)"""
+    N, H, W_, Cc = x.shape
+    ldx = _nhwc_f32(x)
+    stride, pad = int(stride), int(pad)
+    if stride not in (1, 2) or pad not in (0, 1) or H + 2 * pad < 3 or W_ + 2 * pad < 3:
+        raise ValueError(f"pool3_f32: a {H} x {W_} map, stride {stride}, padding {pad}: stride 1 or 2, padding 0 or 1, one window at least")
+    shape = (N, (H + 2 * pad - 3) // stride + 1, (W_ + 2 * pad - 3) // stride + 1, Cc)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == shape and out.device == x.device
+    L.check(L.load().udt_pool3_f32(_ptr(x), _ptr(out), N, H, W_, Cc, ldx, _nhwc_f32(out), stride, pad, int(bool(average)), _stream()),
+            "udt_pool3_f32")
+    return out
+
+
+def fid_input(samples: torch.Tensor, images: torch.Tensor, quantise: bool = True, size: int = 299,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the Inception input of N pairs in one launch (udt_fid_input_f32): samples fp32 [N, 3, H, W] in [0, 1], images fp32 [N, 3, H, W]
+    in [-1, 1] -> fp32 [2 N, size, size, 3] channels-last in [-1, 1], the samples' frames first"""
+    for t in (samples, images):
+        assert t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == 3 and t.is_contiguous()
+    assert samples.shape == images.shape and samples.device == images.device
+    N, _, H, W_ = samples.shape
+    size = int(size)
+    if out is None:
+        out = torch.empty((2 * N, size, size, 3), dtype=torch.float32, device=samples.device)
+    assert tuple(out.shape) == (2 * N, size, size, 3) and out.device == samples.device
+    L.check(L.load().udt_fid_input_f32(_ptr(samples), _ptr(images), _ptr(out), N, H, W_, size, _nhwc_f32(out), int(bool(quantise)),
+                                       _stream()), "udt_fid_input_f32")
+    return out
+
+
+def mean_pixels_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """global average pool of a channels-last fp32 map [N, h, w, C] -> fp32 [N, C] (udt_mean_pixels_f32); ``out`` may have a row
+    stride > C"""
+    N, h, w_, Cc = x.shape
+    ldx = _nhwc_f32(x)
+    if out is None:
+        out = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (N, Cc) and out.stride(1) == 1 and out.device == x.device
+    ldo = out.stride(0) if N > 1 else Cc
+    assert ldo >= Cc
+    L.check(L.load().udt_mean_pixels_f32(_ptr(x), _ptr(out), N, h * w_, Cc, ldx, ldo, _stream()), "udt_mean_pixels_f32")
+    return out
+
+
+def moments_accum_f64(x: torch.Tensor, total: torch.Tensor, outer: torch.Tensor) -> None:
+    """total fp64 [D] += the column sums of x fp32 [n, D] (row stride >= D), outer fp64 [D, D] += x^T x, in fp64 on the f64 MFMA
+    (udt_moments_accum_f64)"""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    n, D = x.shape
+    ld = x.stride(0) if n > 1 else D
+    assert ld >= D
+    for t, shape in ((total, (D,)), (outer, (D, D))):
+        assert t.dtype == torch.float64 and tuple(t.shape) == shape and t.is_contiguous() and t.device == x.device
+    L.check(L.load().udt_moments_accum_f64(_ptr(x), _ptr(total), _ptr(outer), n, D, ld, _stream()), "udt_moments_accum_f64")
+
+
 def crop_resize_aa_bwd(d_out: torch.Tensor, boxes: torch.Tensor, img_shape, mul: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """the adjoint of ``crop_resize_aa`` (udt_crop_resize_aa_bwd_f32): d_out fp32 [N, C, oh, ow], the same DEVICE int32 boxes [N, 5]
     -> d_img fp32 ``img_shape`` = [B, C, H, W], every element written (zero outside the boxes and for images without one).

@@ -453,9 +453,31 @@ def lpips_of(outputs, batches, lpips, chunk: int = 32) -> list:
 
 
 @torch.no_grad()
+def fid_of(outputs, batches, fid, chunk: int = 32):
+    """the FID statistics of every generated frame (the fake set) and of the image it was made from (the real set) — reference
+    metrics.py:5-10 on the frames test.py saves: ``outputs`` is ``predict_many``'s list (only the samples are read), ``batches`` the
+    batches it was given (their ``image``, [-1, 1]); ``fid`` a ``udifftext_amd.fid_inception.FID``.  The pairs go through
+    ``FIDStats.update`` in chunks of at most ``chunk`` consecutive pairs of one image size, as ``lpips_of`` forms them; nothing is
+    copied to the host.  -> the ``FIDStats`` (``compute()`` is the distance, ``state()`` what ranks add)."""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk must be a positive count, not {chunk!r}")
+    if len(outputs) != len(batches):
+        raise ValueError(f"{len(outputs)} outputs for {len(batches)} batches")
+    stats = fid.stats()
+
+    def feed(samples, images):
+        stats.update(samples, images)
+        return samples.new_zeros((samples.shape[0],))
+
+    lpips_of(outputs, batches, feed, chunk=chunk)              # (its chunk former; the zeros it gathers are dropped)
+    return stats
+
+
+@torch.no_grad()
 def evaluate(cfgs, model, sampler, batches, predictor, device: Optional[torch.device] = None, in_flight: Optional[int] = None,
              fuse: Optional[int] = None, image_seeds: Optional[list] = None, ocr_batch: Optional[int] = 64,
-             return_samples: bool = False, lpips=None, lpips_chunk: int = 32) -> dict:
+             return_samples: bool = False, lpips=None, lpips_chunk: int = 32, fid=None, fid_chunk: int = 32) -> dict:
     """reference test.py:74-91 in throughput mode: generate with ``predict_many``, read the text back with the OCR predictor, count
     the exact matches — the sequence accuracy UDiffText is judged by.
     Every batch carries ``label`` (one string per image) and ``r_bbox`` ([B, 4] host integers: top, bottom, left, right of the text
@@ -472,13 +494,22 @@ def evaluate(cfgs, model, sampler, batches, predictor, device: Optional[torch.de
     ``lpips`` (a ``udifftext_amd.lpips_alex.LPIPS``, or anything callable as lpips(samples, images) -> [n]): the reference's second
     measurement (test.py:122-124) on the same frames — the result also carries "lpips" (the mean over all images), "lpips_sum"
     (ranks add "lpips_sum" and "total") and "lpips_per_image" (per batch, input order), from ``lpips_of`` in chunks of
-    ``lpips_chunk`` pairs.  Without it nothing changes: the same keys, the same launches, the same samples."""
+    ``lpips_chunk`` pairs.  Without it nothing changes: the same keys, the same launches, the same samples.
+    ``fid`` (a ``udifftext_amd.fid_inception.FID``): the reference's third measurement (test.py:119-121) on the same frames, fake set =
+    the samples, real set = the batches' images, from ``fid_of`` in chunks of ``fid_chunk`` pairs — the result also carries "fid" (a
+    float; None with "fid_note" when fewer than 2 images leave no covariance) and "fid_stats" (``FIDStats.state()``: n, sum, outer
+    per set as CPU float64 tensors; ranks add them and call ``FIDStats.from_state(...).compute()``).  "fid_note" also says when
+    total < 2048 leaves the covariances rank-deficient, as pytorch_fid warns.  Without it nothing changes either."""
     if ocr_batch is not None and int(ocr_batch) < 1:
         raise ValueError(f"ocr_batch must be a positive count or None, not {ocr_batch!r}")
     if lpips is not None:
         if int(lpips_chunk) < 1:
             raise ValueError(f"lpips_chunk must be a positive count, not {lpips_chunk!r}")
         _lpips_shapes(batches, lpips)
+    if fid is not None:
+        if int(fid_chunk) < 1:
+            raise ValueError(f"fid_chunk must be a positive count, not {fid_chunk!r}")
+        _lpips_shapes(batches, None)
     labels, boxes = [], []
     for k, batch in enumerate(batches):
         lb, rb = _host_boxes(batch, k)
@@ -507,6 +538,17 @@ def evaluate(cfgs, model, sampler, batches, predictor, device: Optional[torch.de
         res["lpips_per_image"] = per
         res["lpips_sum"] = float(sum(v for vs in per for v in vs))
         res["lpips"] = res["lpips_sum"] / total if total else 0.0
+    if fid is not None:
+        stats = fid_of(outputs, batches, fid, chunk=fid_chunk)
+        res["fid_stats"] = stats.state()
+        if total < 2:
+            res["fid"] = None
+            res["fid_note"] = f"FID needs at least 2 images per set for a covariance, not {total}"
+        else:
+            res["fid"] = stats.compute()
+            if total < stats.dim:
+                res["fid_note"] = (f"{total} images for {stats.dim} features: the covariances are rank-deficient, and the number is "
+                                   "not comparable with one from a larger set")
     if return_samples:
         res["outputs"] = outputs
     return res
