@@ -157,7 +157,8 @@ def pack_linear_fp8(w: torch.Tensor, n_pad_to: int = 4):
     Np, Kp = _round_up(N, n_pad_to), _round_up(K, FP8_KPAD)
     wf = w.float()
     amax = wf.abs().amax(dim=1).clamp_min(1e-12)
-    scale = amax / FP8_MAX
+    # amax * fp32(1 / 448), written out: what udt_pack_linear computes, on any device (a CPU tensor divided by 448 rounds differently)
+    scale = amax * torch.tensor(1.0 / FP8_MAX, dtype=torch.float32, device=w.device)
     q = (wf / scale[:, None]).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
     out = torch.zeros((Np, Kp), dtype=torch.uint8, device=w.device)
     out[:N, :K] = q
